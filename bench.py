@@ -14,8 +14,8 @@ weak scaling, record-sharded, no data-path collective; the control plane
 (barrier, max of per-rank times, per-rank summary digests against the
 oracle's, tests/golden/summaries.json config3_shards) goes over
 torch.distributed (gloo).  Rank 0's shard is the N = 1 workload itself, so
-the 1 -> N curve is like for like.  Every line also carries BASELINE config 4
-as "config4": the fixed 4 KiB block shard (2^26 blocks = 256 GiB per GPU,
+the 1 -> N curve is like for like.  With --full every line also carries BASELINE
+config 4 as "config4": the fixed 4 KiB block shard (2^26 blocks = 256 GiB per GPU,
 shard r = blocks [r*2^26, (r+1)*2^26) of config 2's stream), timed the same
 way after the config-3 buffers are freed.  --config 2 / 1 run the fixed 4 KiB
 blocks (64 GiB; config 4's shard at N > 1) / the 256 B WAL payloads.
@@ -26,7 +26,22 @@ blocks (64 GiB; config 4's shard at N > 1) / the 256 B WAL payloads.
 WORLD_SIZE must equal --gpus.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3|2|1]
-                  [--blocks-per-gpu B] [--no-cpu-baseline]
+                  [--blocks-per-gpu B] [--dump-outputs DIR] [--full] [--no-cpu-baseline]
+
+A plain run does what the headline figure needs and no more: it sets up, warms
+up, times the K steps, writes --dump-outputs if asked and prints the line.
+--full adds every other measurement and check to the same line, each with its
+own --no-* switch: the host round trip, the summary digests against the
+oracle's, the CPU baselines, the loads-only ceiling and the config-4 sub-line.
+
+--dump-outputs DIR writes what the last timed step left in the output buffer --
+the per-record digests a caller of lsmck_crc32_batch* / lsmck_sha256_batch*
+receives -- as DIR/crc32.npy (float64 [n]: the CRC values, exact) or
+DIR/sha256.npy (float64 [n, 32]: the digest bytes), rank r > 0 as
+DIR/<name>_rank<r>.npy.  Where the ranks' arrays together would pass 32 MiB,
+each is cut to a fixed, seeded sample of its records (distinct, in index order,
+an equal share of the 32 MiB), the same in every run with the same arguments;
+the inputs are seeded too, so two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md section 5 for every field).
 """
@@ -74,6 +89,12 @@ def parse():
                     help="blocks per rank of the config-4 sub-measurement (default 2^26; 2^26/N when the ranks "
                          "share one GPU)")
     ap.add_argument("--blocks-per-gpu", type=int, default=0, help="override the per-GPU record count")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: host round trip, summary digests against the oracle's, CPU "
+                         "baselines, loads-only ceiling and the config-4 sub-line (each has a --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's per-record digests as DIR/<name>.npy (a seeded sample of "
+                         "the records where all ranks' arrays together would pass 32 MiB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-records", type=int, default=0)
     ap.add_argument("--variants", default="",
@@ -177,6 +198,36 @@ def config3_shard(gen, seed, nrec, rank, gather=None, framed=False, align=1):
     nbytes = int(offs[-1]) + int(lens[-1])
     byte_off = sum(gather(nbytes)[:rank]) if gather else 0
     return offs, lens, nbytes, byte_off
+
+
+DUMP_MAX_BYTES = 32 << 20  # all ranks' arrays together, well inside the 64 MB a dump may take
+DUMP_SEED = 0xD0F5EED
+
+
+def dump_sample(nrec, keep):
+    """`keep` distinct record indices of [0, nrec), increasing: one seeded draw
+    from each of `keep` equal strata, so the sample spans the whole batch."""
+    start = (np.arange(keep + 1, dtype=np.uint64) * np.uint64(nrec)) // np.uint64(keep)
+    jitter = np.random.default_rng(DUMP_SEED).integers(0, nrec // keep, size=keep, dtype=np.uint64)
+    return (start[:-1] + jitter).astype(np.int64)  # nrec // keep <= every stratum's width
+
+
+def dump_outputs(dirname, out, nrec, sha, rank, world=1):
+    """--dump-outputs: the output buffer of the last timed step as float64 (a
+    u32 CRC or a digest byte is exact in it), every record or -- where the
+    ranks' arrays together would pass 32 MiB -- a fixed, seeded sample of them
+    in index order (dump_sample), each rank an equal share of the 32 MiB."""
+    width = 32 if sha else 1
+    keep = DUMP_MAX_BYTES // world // (8 * width)
+    if sha:
+        arr = out.download(np.uint8, count=32 * nrec).reshape(nrec, 32)
+    else:
+        arr = out.download(np.uint32, count=nrec)
+    if nrec > keep:
+        arr = arr[dump_sample(nrec, keep)]
+    os.makedirs(dirname, exist_ok=True)
+    name = ("sha256" if sha else "crc32") + (f"_rank{rank}" if rank else "")
+    np.save(os.path.join(dirname, name + ".npy"), arr.astype(np.float64))
 
 
 def config4_sub(a, ctx, stream, sptr, world, rank):
@@ -405,6 +456,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall_max = float(t[0])
 
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, out, nrec, sha, rank, world)
+
     ms_per_step = wall_max * 1000.0 / a.steps
     total_payload = payload * world
     value = total_payload / GIB / (wall_max / a.steps)
@@ -503,7 +557,7 @@ def main():
     # a sample of the same records in pinned host memory, one synchronous
     # lsmck_crc32_batch* per step = H2D DMA + kernel + D2H, chunked and
     # double-buffered inside liblsmck.  Reported beside `value`, never as it.
-    if rank == 0 and world == 1 and not a.no_host_roundtrip and not sha:
+    if a.full and rank == 0 and world == 1 and not a.no_host_roundtrip and not sha:
         if cfg == 3 or a.desc:
             hn = min(nrec, 1 << 21)
             hbytes = int(offs[hn - 1]) + int(lens[hn - 1])
@@ -539,13 +593,15 @@ def main():
     # summary digest: CRC-32 of the little-endian output array
     # (CRCs, or the 32-B digests), for cross-run comparison; every rank's, for N > 1
     import zlib
-    mine = "%08x" % zlib.crc32(out.download(np.uint8, count=(32 if sha else 4) * nrec).tobytes())
-    if world > 1:
-        allsum = [None] * world
-        dist.all_gather_object(allsum, mine)
-    else:
-        allsum = [mine]
-    if rank == 0:
+    allsum = []
+    if a.full:
+        mine = "%08x" % zlib.crc32(out.download(np.uint8, count=(32 if sha else 4) * nrec).tobytes())
+        if world > 1:
+            allsum = [None] * world
+            dist.all_gather_object(allsum, mine)
+        else:
+            allsum = [mine]
+    if a.full and rank == 0:
         res["summary_crc32"] = allsum[0]
         for pr, sm in zip(res["per_rank"], allsum):
             pr["summary_crc32"] = sm
@@ -569,7 +625,7 @@ def main():
                 res["summary_matches_oracle"] = res["summary_crc32"] == g
 
     # CPU baseline + parity of the same sample (rank 0, N = 1 only)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and sha:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and sha:
         from oracle import oracle as O  # the checker / baseline, never the measured path
         ns = min(nrec, a.cpu_sample_records or (1 << 16))
         if cfg == 3:
@@ -607,7 +663,7 @@ def main():
             "openssl_hashlib_1_thread": {"value": round(sbytes / GIB / tossl, 3), "unit": "GiB/s", "cores": 1},
             "sample": "the cpu_baseline sample",
         }
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not sha:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not sha:
         from oracle import oracle as O  # the checker / baseline, never the measured path
         if cfg == 3:
             ns = a.cpu_sample_records or (1 << 21)
@@ -664,7 +720,7 @@ def main():
     # kernel and launch with crc_ablate 3 -- payload loads only, no checksum,
     # no store -- on the same buffer, timed like the bench line.  Last: it
     # leaves `out` invalid, so every check of `out` above runs first.
-    if rank == 0 and world == 1 and not sha and not a.no_stream_ceiling and ab is None:
+    if a.full and rank == 0 and world == 1 and not sha and not a.no_stream_ceiling and ab is None:
         ctx.set_option("crc_ablate", 3)
         try:
             step()
@@ -686,7 +742,7 @@ def main():
 
     # BASELINE config 4 beside the config-3 line: the per-GPU fixed-block shard
     # (its own 1 -> N curve from the same runs), after config 3's buffers go
-    if cfg == 3 and not sha and not a.no_config4:
+    if a.full and cfg == 3 and not sha and not a.no_config4:
         data.free()
         out.free()
         for b in (d_off, d_len):

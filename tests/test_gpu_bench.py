@@ -7,7 +7,10 @@
   tests/golden/summaries.json config3_shards_small); its config-4 sub-line
   likewise (digests computed here).  The two ranks share the box's one GPU
   (LSMCK_BENCH_SHARE_GPU=1) on reduced shards.  --config 2 keeps the
-  config-4 shard as the main line.
+  config-4 shard as the main line.  These lines are read from `--full` runs:
+  the digests and the config-4 sub-line are not part of a plain run.
+* A plain run (`--gpus 1 --steps K --warmup W`) carries the headline fields
+  only, and `--dump-outputs DIR` holds the last timed step's CRCs.
 * Config 4's per-GPU shard at full size (2^26 x 4 KiB = 256 GiB, rank 0's
   blocks [0, 2^26) of config 2's stream) through the C ABI, against the
   oracle's summary digest (tests/golden/make_summaries.py config4).
@@ -37,7 +40,8 @@ def _bench2(*args, gpus=2, timeout=300):
     env = dict(os.environ, LSMCK_BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "3",
-                        "--warmup", "1", *args], cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
+                        "--warmup", "1", "--full", *args], cwd=ROOT, env=env, capture_output=True, text=True,
+                       timeout=timeout)
     assert p.returncode == 0, p.stderr[-3000:]
     return json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][-1])
 
@@ -95,8 +99,8 @@ def test_bench_gpus2_launches_two_ranks():
     env = dict(os.environ, LSMCK_BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "2",
-                        "--blocks-per-gpu", str(nrec), "--steps", "3", "--warmup", "1"], cwd=ROOT, env=env,
-                       capture_output=True, text=True, timeout=300)
+                        "--blocks-per-gpu", str(nrec), "--steps", "3", "--warmup", "1", "--full"], cwd=ROOT,
+                       env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [x for x in p.stdout.splitlines() if x.startswith("{")][-1]
     r = json.loads(line)
@@ -135,6 +139,140 @@ def test_bench_world_size_mismatch_fails():
                        capture_output=True, text=True, timeout=120)
     assert p.returncode == 2
     assert "WORLD_SIZE=2" in p.stderr
+
+
+class _HostOut:
+    """dump_outputs' view of a device buffer, over host bytes"""
+
+    def __init__(self, raw):
+        self.raw = np.ascontiguousarray(raw).view(np.uint8)
+
+    def download(self, dtype=np.uint8, count=None, offset=0):
+        return self.raw.view(dtype)[:count].copy()
+
+
+def test_bench_dump_outputs_whole(tmp_path):
+    """--dump-outputs: an output inside the budget is dumped whole, as float64."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(7)
+    crc = rng.integers(0, 1 << 32, 1000, dtype=np.uint64).astype(np.uint32)
+    bench.dump_outputs(str(tmp_path / "a"), _HostOut(crc), crc.size, False, 0)
+    got = np.load(tmp_path / "a" / "crc32.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, crc.astype(np.float64))
+    dig = rng.integers(0, 256, (50, 32), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), _HostOut(dig), 50, True, 3)
+    got = np.load(tmp_path / "a" / "sha256_rank3.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, dig.astype(np.float64))
+
+
+MULT = 2654435761  # odd: i -> i * MULT mod 2^32 is one to one, so a dumped value names its record
+
+
+def _records_of(values):
+    return (values.astype(np.uint64) * np.uint64(pow(MULT, -1, 1 << 32))) % np.uint64(1 << 32)
+
+
+def test_bench_dump_outputs_sample(tmp_path):
+    """A large output is dumped as a sample: the same one every time, float64,
+    distinct records in index order, one from every stratum of the batch (so it
+    spans the whole output), and all ranks' files together under 64 MB."""
+    sys.path.insert(0, ROOT)
+    import bench
+    keep = bench.DUMP_MAX_BYTES // 8
+    n = 3 * keep + 7
+    big = (np.arange(n, dtype=np.uint64) * np.uint64(MULT) % np.uint64(1 << 32)).astype(np.uint32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), _HostOut(big), n, False, 0)
+    b, c = np.load(tmp_path / "b" / "crc32.npy"), np.load(tmp_path / "c" / "crc32.npy")
+    assert b.dtype == np.float64 and b.shape == (keep,) and np.array_equal(b, c)
+    assert os.path.getsize(tmp_path / "b" / "crc32.npy") <= 64 * 10**6
+    idx = _records_of(b)
+    assert np.all(np.diff(idx.astype(np.int64)) > 0) and idx[-1] < n
+    edges = (np.arange(keep + 1, dtype=np.uint64) * np.uint64(n)) // np.uint64(keep)
+    assert np.all(idx >= edges[:-1]) and np.all(idx < edges[1:])
+    assert np.any(idx != edges[:-1])  # drawn, not a plain stride
+    # one past the limit still samples, and exactly `keep` distinct records
+    bench.dump_outputs(str(tmp_path / "d"), _HostOut(big), keep + 1, False, 0)
+    d = _records_of(np.load(tmp_path / "d" / "crc32.npy"))
+    assert d.shape == (keep,) and np.all(np.diff(d.astype(np.int64)) > 0) and d[-1] <= keep
+    # N ranks share the budget: every rank's file counted
+    for world in (2, 8):
+        out = tmp_path / f"w{world}"
+        for rank in range(world):
+            bench.dump_outputs(str(out), _HostOut(big), n, False, rank, world)
+        files = sorted(os.listdir(out))
+        assert files == sorted(["crc32.npy"] + [f"crc32_rank{r}.npy" for r in range(1, world)])
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 * 10**6
+        for f in files:
+            r = _records_of(np.load(out / f))
+            assert r.shape == (keep // world,) and np.all(np.diff(r.astype(np.int64)) > 0) and r[-1] < n
+    dig = np.repeat(big[:keep // 8].view(np.uint8).reshape(-1, 4), 8, axis=1)  # [n, 32] digests
+    bench.dump_outputs(str(tmp_path / "s"), _HostOut(dig), dig.shape[0], True, 0)
+    s = np.load(tmp_path / "s" / "sha256.npy")
+    assert s.dtype == np.float64 and s.shape == (keep // 32, 32) and s.nbytes <= bench.DUMP_MAX_BYTES
+    sidx = _records_of(np.ascontiguousarray(s[:, ::8].astype(np.uint8)).view(np.uint32).ravel())
+    assert np.all(np.diff(sidx.astype(np.int64)) > 0) and sidx[-1] < dig.shape[0]
+    assert np.array_equal(s, dig[sidx.astype(np.int64)].astype(np.float64))
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run carries the headline fields and none of --full's legs, takes
+    --steps timed steps, and --dump-outputs holds the last step's CRCs: every
+    record's equals the oracle's."""
+    nrec = 1 << 14
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                        "--blocks-per-gpu", str(nrec), "--dump-outputs", str(tmp_path)], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-3000:]
+    r = json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][-1])
+    assert r["steps"] == 4 and r["warmup"] == 1 and r["n_gpus"] == 1
+    assert r["unit"] == "GiB/s" and r["higher_is_better"] is True and r["dtype"] == "u8"
+    assert r["metric"].startswith("GiB/s device-resident batched record checksum")
+    assert r["config"]["workload"].startswith("config3") and r["config"]["records_per_gpu"] == nrec
+    assert r["ms_per_step"] > 0
+    pay = r["config"]["payload_bytes_per_gpu"]
+    assert abs(r["value"] - pay / 2**30 / (r["ms_per_step"] * 1e-3)) / r["value"] < 0.01
+    assert r["cpu_baseline"] is None
+    for k in ("config4", "host_roundtrip", "cpu_extra", "summary_crc32", "summary_matches_oracle"):
+        assert k not in r
+    assert "loads_only_ceiling" not in r["roofline"]
+    lens = O.gen_zipf_lengths(0x5EED0003, nrec)
+    offs = np.zeros(nrec, dtype=np.uint64)
+    np.cumsum(lens[:-1].astype(np.uint64), out=offs[1:])
+    data = O.gen_stream(0x5EED0003, 0, int(offs[-1]) + int(lens[-1]))
+    got = np.load(tmp_path / "crc32.npy")
+    assert got.dtype == np.float64
+    assert np.array_equal(got, O.crc32_batch(data, offs, lens).astype(np.float64))
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_sampled_on_gpu(tmp_path):
+    """An output past the dump budget (config 1, 2^22 + 8 records of 256 B: 8
+    records over) is dumped as 2^22 sampled CRCs: sample i is the oracle's CRC
+    of a record in stratum i of the batch."""
+    sys.path.insert(0, ROOT)
+    import bench
+    keep = bench.DUMP_MAX_BYTES // 8
+    nrec = keep + 8
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--config", "1", "--blocks-per-gpu", str(nrec), "--dump-outputs", str(tmp_path)], cwd=ROOT,
+                       env=env, capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-3000:]
+    r = json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][-1])
+    assert r["config"]["records_per_gpu"] == nrec and r["steps"] == 2
+    got = np.load(tmp_path / "crc32.npy")
+    assert got.dtype == np.float64 and got.shape == (keep,)
+    want = O.crc32_fixed(O.gen_stream(0x5EED0001, 0, nrec * 256), 256, 256, nrec, threads=16).astype(np.float64)
+    edges = (np.arange(keep + 1, dtype=np.uint64) * np.uint64(nrec)) // np.uint64(keep)
+    lo, hi = edges[:-1].astype(np.int64), edges[1:].astype(np.int64)
+    assert (hi - lo).max() <= 2  # so a stratum is its first and last record
+    assert np.all((got == want[lo]) | (got == want[hi - 1]))
 
 
 @pytest.mark.gpu

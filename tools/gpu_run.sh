@@ -36,9 +36,9 @@ has pytest && step pytest 1100 python3 -u -m pytest tests -m gpu -q -rf --timeou
 # the driver's default line, then the same command (no host round trip: its
 # staged host batches run the stream kernel too) under the kernel trace, so the
 # line's HIP-event launch time and the trace's durations come from the same launches
-has bench && step bench 400 python3 bench.py
+has bench && step bench 400 python3 bench.py --full
 if has benchkt; then
-  step benchkt 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_c3 -o kt -- python3 bench.py --no-host-roundtrip
+  step benchkt 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_c3 -o kt -- python3 bench.py --full --no-host-roundtrip
   python3 tools/kt_stats.py $O/kt_c3 > $O/kt_stats_c3.txt 2>&1
 fi
 if has c3pmc; then  # HBM bytes per launch of the stream kernel (separate FETCH_SIZE / WRITE_SIZE passes)
@@ -60,7 +60,7 @@ if has waldiag; then
   step waldiagkt 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_waldev -o kt -- python3 tools/wal_kt.py
   python3 tools/kt_stats.py $O/kt_waldev > $O/kt_stats_waldev.txt 2>&1
 fi
-has sha && step sha 400 python3 bench.py --digest sha256 --steps 5 --warmup 1 --no-config4
+has sha && step sha 400 python3 bench.py --full --digest sha256 --steps 5 --warmup 1
 has shaab && step shaab 600 python3 bench.py --digest sha256 --variants=${SHA_VARIANTS:--,t6,t16} --rounds 3 --steps 3 --warmup 1 --no-cpu-baseline --no-host-roundtrip --no-config4
 has tree && step tree 900 python3 -u tools/e2e_tree.py --gib 16 --reps 2 --multi 2 --dir /dev/shm/lsm_e2e_$R
 has server && step server 1100 python3 -u tools/e2e_server.py --gib 100 --dir /dev/shm/lsm_e2e_server_$R
