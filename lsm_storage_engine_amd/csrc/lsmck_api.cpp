@@ -571,7 +571,7 @@ int crc_fixed_device(lsmck_ctx* ctx, const uint8_t* base, size_t stride, uint32_
     HIPCHK(hipMemsetAsync(out, 0, n * 4, st));
     return 0;
   }
-  uint64_t nsegr = (len + 127u) / 128u;
+  uint64_t nsegr = ((uint64_t)len + 127u) / 128u;  // 64-bit: len + 127 wraps in 32 bits above 2^32 - 128
   uint64_t per = kMaxSegsPerLaunch / nsegr;
   // every record is stored whole by one lane when no record straddles a
   // 64-segment tile; otherwise partial results are XOR-accumulated into zeros
@@ -724,7 +724,9 @@ void stage_copy(lsmck_ctx* ctx, uint8_t* dst, const uint8_t* src, size_t n, unsi
     memcpy(dst, src, n);
     return;
   }
-  const size_t part = ((n / threads) + 4095) & ~(size_t)4095;
+  // ceil(n / threads), then up to 4 KiB: with floor, an n whose quotient is a
+  // multiple of 4 KiB left its last n % threads bytes uncopied
+  const size_t part = (((n + threads - 1) / threads) + 4095) & ~(size_t)4095;
   host_pool(ctx).run(threads, [=](unsigned t) {
     const size_t a = std::min(n, t * part), b = std::min(n, (t + 1) * part);
     if (a < b) memcpy(dst + a, src + a, b - a);
@@ -1356,7 +1358,7 @@ int lsmck_crc32_batch_fixed(lsmck_ctx* ctx, const uint8_t* base, size_t stride, 
   int rc = check_ctx(ctx);
   if (rc) return rc;
   if (n && !out) return lsmck_host::set_error(LSMCK_EINVAL, "null output");
-  if (n > 1 && stride < len) return lsmck_host::set_error(LSMCK_EINVAL, "stride < len");
+  // (stride < len is allowed: the records overlap, every kernel indexes by i * stride and only reads)
   std::lock_guard<std::mutex> lk(ctx->mu);
   DevGuard g(ctx->dev);
   if (flags & LSMCK_DEVICE) return crc_fixed_device(ctx, base, stride, len, n, out, pick_stream(ctx, stream));

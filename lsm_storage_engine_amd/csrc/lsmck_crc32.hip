@@ -73,6 +73,10 @@ __device__ __forceinline__ uint32_t gf2_mulmod(uint32_t a, uint32_t b) {
   return p;
 }
 
+// 128-byte segments of a non-empty record: ceil(len / 128) for every uint32_t
+// len -- (len + 127) >> 7 wraps to 0 for the top 127 lengths (len > 2^32 - 128).
+__host__ __device__ __forceinline__ uint32_t segs_of(uint32_t len) { return (len >> 7) + ((len & 127u) != 0u); }
+
 // The kernels declare no static LDS, so the dynamic region starts at LDS
 // address 0: index an address_space(3) pointer directly (indexing smem + a
 // costs a v_add of the relocated base per lookup).
@@ -445,13 +449,13 @@ template <bool FAST, int CHAINS, int ABLATE = 0, bool PERCOL = false>
 __global__ __launch_bounds__(1024) void crc32_fixed_kernel(CrcParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   build_lds_tables(smem, P);
-  if (PERCOL) build_lds_cols(P, (P.flen + 127u) >> 7);
+  if (PERCOL) build_lds_cols(P, segs_of(P.flen));
   __syncthreads();
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t lo = (lane & 31u) * 4u, hi = lo | 0x10000u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);  // uniform: scalar loop control
   const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
-  const uint32_t nsegr = (P.flen + 127u) >> 7;
+  const uint32_t nsegr = segs_of(P.flen);
   const uint32_t total = nsegr * (uint32_t)P.nrec;  // host keeps this < 2^32 - 64
   const uint32_t ntiles = (total + 63u) >> 6;
   // ping-pong between two load slots A/B: a loaded register is never copied
@@ -609,7 +613,7 @@ __global__ __launch_bounds__(1024) void crc32_wring_kernel(CrcParams P) {
 // run's last segment) become empty first segments (they load only the zero
 // buffer and store nothing)
 __device__ __forceinline__ void desc_map_complete(SegInfo& si) {
-  const uint32_t nseg = si.rec_len ? (si.rec_len + 127u) >> 7 : 1u;
+  const uint32_t nseg = si.rec_len ? segs_of(si.rec_len) : 1u;
   si.k = nseg - 1u - si.q;
   if (!si.valid) {
     si.q = 0;
@@ -623,7 +627,7 @@ __device__ __forceinline__ void desc_map_complete(SegInfo& si) {
 // consecutive segments; walk_phase1 reduces nseg per WALK_SB-record
 // superblock (four records per thread, one 16-byte load) and scan_phase2
 // scans the superblock sums in u64.
-__device__ __forceinline__ uint32_t rec_nseg(uint32_t len) { return len ? (len + 127u) >> 7 : 1u; }
+__device__ __forceinline__ uint32_t rec_nseg(uint32_t len) { return len ? segs_of(len) : 1u; }
 
 // the thread's four lengths (records >= n read as "absent": own = false)
 __device__ __forceinline__ void load_len4(const uint32_t* __restrict__ len, uint64_t n, uint64_t r0, uint32_t l[4]) {
@@ -896,7 +900,7 @@ __global__ __launch_bounds__(1024) void crc32_walk_kernel(CrcParams P) {
     si.rec_len = in_c ? ln_c : ln_n;
     si.k = 0;
     // (defensive: a lane never addresses a segment its record does not have)
-    si.valid = si.valid && si.q < (si.rec_len ? (si.rec_len + 127u) >> 7 : 1u);
+    si.valid = si.valid && si.q < (si.rec_len ? segs_of(si.rec_len) : 1u);
     desc_map_complete(si);  // k; pad lanes become empty first segments
     // cursor for the next tile: the record holding segment G + 64
     const uint32_t rec63 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(rec - wc0), 63);
@@ -1670,7 +1674,7 @@ static int launch_wring(const CrcParams* P, int ncu, hipStream_t st) {
 // variant bits 8-11: crc_ablate (3: payload loads only, ring kernel)
 extern "C" int lsmk_launch_crc32_fixed(const CrcParams* P, int ncu, int variant, hipStream_t st) {
   const bool fast = ((uintptr_t)P->base % 4 == 0) && (P->stride % 4 == 0) && (P->flen % 128 == 0);
-  const uint32_t nsegr = (P->flen + 127u) >> 7;
+  const uint32_t nsegr = segs_of(P->flen);
   const bool percol = (64u % nsegr) == 0;
   const bool buf_ok = (uint64_t)P->stride * 65u + P->flen < (1ull << 31);
   const int ablate = (variant >> 8) & 0xF;
