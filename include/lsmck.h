@@ -329,7 +329,10 @@ int lsmck_crc32_verify_batch(lsmck_ctx* ctx, const uint8_t* base, const uint64_t
                              uint64_t* first_bad);
 
 /* SHA-256 of n messages -> out32[32*i .. 32*i+32).  The batch form of
- * calculate_checksum's digest (src/checksums.rs:20-38). */
+ * calculate_checksum's digest (src/checksums.rs:20-38).  Messages may lie in
+ * any order, overlap and repeat.  Fixed form: message i = base[i*stride ..
+ * i*stride+len), any stride as for lsmck_crc32_batch_fixed: with stride < len
+ * the messages overlap (host batches ship the span once). */
 int lsmck_sha256_batch(lsmck_ctx* ctx, const uint8_t* base, const uint64_t* off, const uint32_t* len, size_t n,
                        uint8_t* out32, unsigned flags, void* stream);
 int lsmck_sha256_batch_fixed(lsmck_ctx* ctx, const uint8_t* base, size_t stride, uint32_t len, size_t n,

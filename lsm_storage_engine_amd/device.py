@@ -228,21 +228,23 @@ class Context:
         return rc, nb.value, fb.value
 
     # --- SHA-256 --------------------------------------------------------------
-    def sha256(self, data, off, length):
+    def sha256(self, data, off, length, pinned=False):
         data = np.ascontiguousarray(data, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
         length = np.ascontiguousarray(length, dtype=np.uint32)
         n = len(off)
         out = np.empty((n, 32), dtype=np.uint8)
+        flags = _lib.HOST_PINNED if pinned else _lib.HOST
         _lib.check(self.lib.lsmck_sha256_batch(self.handle, data.ctypes.data, off.ctypes.data, length.ctypes.data, n,
-                                               out.ctypes.data, _lib.HOST, None), "sha256_batch")
+                                               out.ctypes.data, flags, None), "sha256_batch")
         return out
 
-    def sha256_fixed(self, data, stride, length, n):
+    def sha256_fixed(self, data, stride, length, n, pinned=False):
         data = np.ascontiguousarray(data, dtype=np.uint8)
         out = np.empty((n, 32), dtype=np.uint8)
+        flags = _lib.HOST_PINNED if pinned else _lib.HOST
         _lib.check(self.lib.lsmck_sha256_batch_fixed(self.handle, data.ctypes.data, stride, length, n,
-                                                     out.ctypes.data, _lib.HOST, None), "sha256_batch_fixed")
+                                                     out.ctypes.data, flags, None), "sha256_batch_fixed")
         return out
 
     def sha256_device(self, base, off, length, n, out, stream=None):
