@@ -84,22 +84,42 @@ def test_desc_random_vs_oracle(ctx, seed):
     assert len(bad) == 0, (bad[:10], ln[bad[:10]], off[bad[:10]])
 
 
-def test_desc_every_first_segment_length(ctx):
-    # all record lengths 0..1030 (every first-segment length, 0-8 segments) at 4 alignments
+def _host_crc(ctx, data, off, ln, crc_stream):
+    """ctx.crc32 on a host batch under the given crc_stream option.  The
+    library stages a host batch itself (its span when sorted and dense, else
+    the records gathered into a packed copy) and hands it to the stream kernel
+    alone (1, the default); with 0 the staged batch goes to the walking kernel
+    alone."""
+    ctx.set_option("crc_stream", crc_stream)
+    try:
+        return ctx.crc32(data, off, ln)
+    finally:
+        ctx.set_option("crc_stream", 1)
+
+
+@pytest.mark.parametrize("crc_stream", [1, 0])
+def test_desc_every_first_segment_length(ctx, crc_stream):
+    """All record lengths 0..1030 (every first-segment length, 0-8 segments) at
+    4 alignments, as a host batch: on the stream kernel (crc_stream 1) and on
+    the walking kernel with its unaligned segment path, seg_issue<false> /
+    seg_finish<false> (crc_stream 0)."""
     ln = np.tile(np.arange(0, 1031, dtype=np.uint32), 4)
     off, total = _packed(ln)
     off = off + np.repeat(np.arange(4, dtype=np.uint64), 1031)
     data = O.gen_stream(7, 0, total + 16)
-    assert np.array_equal(ctx.crc32(data, off, ln), O.crc32_batch(data, off, ln, threads=8))
+    assert np.array_equal(_host_crc(ctx, data, off, ln, crc_stream), O.crc32_batch(data, off, ln, threads=8))
 
 
-def test_desc_scattered_unsorted(ctx):
+@pytest.mark.parametrize("crc_stream", [1, 0])
+def test_desc_scattered_unsorted(ctx, crc_stream):
+    """Overlapping records in any order, as a host batch: the staged batch on
+    the stream kernel (crc_stream 1) and on the walking kernel (crc_stream 0)."""
     rng = np.random.default_rng(9)
     data = O.gen_stream(11, 0, 8 << 20)
     n = 20000
     ln = rng.integers(0, 3000, n).astype(np.uint32)
     off = rng.integers(0, (8 << 20) - 3000, n).astype(np.uint64)  # overlapping, any order
-    assert np.array_equal(ctx.crc32(data, off, ln), O.crc32_batch(data, off, ln, threads=8))
+    assert np.array_equal(_host_crc(ctx, data, off, ln, crc_stream), O.crc32_batch(data, off, ln, threads=8))
 
 
 def test_large_records_high_segment_counts(ctx):
