@@ -44,6 +44,7 @@ extern "C" {
 #define LSMCK_ENOMEM (-12)
 #define LSMCK_EIO (-5)
 #define LSMCK_ENODEV (-19)
+#define LSMCK_ENOSPC (-28) /* lsmck_wal_encode_batch: the image buffer is too small */
 #define LSMCK_EHIP (-1000) /* LSMCK_EHIP - hipError_t */
 
 /* flags for batch calls */
@@ -275,6 +276,11 @@ int lsmck_device_count(void);
  *   "crc_ablate"  diagnostic: 3 = the stream kernel with payload loads only
  *                 (the bench's loads-only ceiling; results are garbage); 2,
  *                 4..12 only in A/B libraries built with -DLSMCK_AB_ABLATIONS.
+ *   "wal_encode_time"  DIAGNOSTIC, not part of the stable option list (it and
+ *                 its stats may change or go with the tool that uses them):
+ *                 1 = lsmck_wal_encode_batch records device events around
+ *                 its stages (tools/wal_encode_big.py reads them back as
+ *                 stats); 0 = none (default).
  * Returns 0, or LSMCK_EINVAL for an unknown key / value. */
 int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value);
 
@@ -292,6 +298,14 @@ int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value);
  *   "numa_node"      the device's NUMA node (sysfs of its PCI function; -1
  *                    unknown), and "stage_numa_node" the node the context's
  *                    pinned buffers and copy threads are placed on (-1: none).
+ *   "wal_encode_tile"  bytes of the image one workgroup of lsmck_wal_encode_batch's
+ *                    gather kernel writes (a power of two, at most 64 KiB;
+ *                    tiles are aligned on the image's address).
+ *   "wal_encode_scan_ns", "wal_encode_gather_ns", "wal_encode_crc_ns",
+ *   "wal_encode_stamp_ns"  DIAGNOSTIC, subject to change: the last lsmck_wal_encode_batch's stages between
+ *                    device events, with "wal_encode_time" 1: the size /
+ *                    validate / scan kernels, the gather, the descriptors and
+ *                    the CRC pass, the stamp.
  * Returns 0 and *value, or LSMCK_EINVAL for an unknown key. */
 int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value);
 
@@ -417,6 +431,62 @@ int lsmck_wal_replay_verify16(lsmck_ctx* ctx, const uint8_t* wal, size_t n, unsi
  * Returns 0 or a negative hipError_t. */
 int lsmck_wal_frame_insert_device(lsmck_ctx* ctx, uint8_t* img, const uint64_t* off, const uint32_t* len,
                                   const uint32_t* crc, size_t n, uint32_t kmax, void* stream);
+
+/* Batch WAL encode: the batch form of CommandLog::log (src/wal.rs:165-196)
+ * for a group commit, a memtable dump or a log built by a GPU-side producer --
+ * the bulk append of the WAL seam, and the inverse of the replay's record
+ * array.  Command i names its key in the `keys` arena and, for an Insert, its
+ * value in the `vals` arena; img[0 .. *img_bytes) becomes byte for byte what
+ * lsmck_wal_encode_insert / lsmck_wal_encode_remove give for commands 0..n-1
+ * in order, concatenated -- the reference appending them one by one to an
+ * empty log.  keys and vals may be the same buffer, and commands may name
+ * overlapping or repeated source ranges; img must not overlap either arena.
+ * On the device (lsmck_wal.hip): the record sizes are checked and scanned
+ * into the record offsets; one gather kernel moves keys, values and header
+ * fields into log order (the image cut into aligned tiles, every 16 aligned
+ * bytes of it written by one 16-byte store); the payload CRCs come from the
+ * dispatcher of lsmck_crc32_batch over the image (a log's payloads are sorted
+ * and a header apart: the stream kernel); one thread per record stamps its CRC.
+ * flags: LSMCK_DEVICE -- keys, vals, cmds (8-byte aligned), img and rec_off
+ * are device pointers; LSMCK_HOST (optionally | LSMCK_HOST_PINNED) -- all of
+ * them are host pointers: the arenas and the commands are uploaded whole, the
+ * log is encoded on the device and the image copied back.  The host form is
+ * staged whole, not pipelined, and its size is bounded by device memory
+ * (arenas + commands + image).  LSMCK_HOST_PINNED is only a hint here: it
+ * selects no other path -- every host buffer goes through hipMemcpyAsync on
+ * the context's stream, which copies straight from and to the pages that are
+ * pinned and stages the others -- so the buffers may be pinned one by one or
+ * not at all.  Any other flag bit is LSMCK_EINVAL.  img_bytes and bad_index are host pointers
+ * either way.  rec_off (optional, n entries) receives record i's header
+ * offset.  Synchronous: the 8-byte total and the validation word are read
+ * back after the offset scan, before anything is written to img.  Scratch
+ * comes from the context; calls on one context serialise on it.
+ * Returns 0 (n == 0: 0 and *img_bytes = 0), or
+ *   LSMCK_EINVAL  a command's type is not 1 or 2; an Insert has klen + vlen >
+ *                 2^32-1 (the reference's reader could not read it back:
+ *                 data_len wraps at wal.rs:129, and the CRC batch takes u32
+ *                 lengths); a non-empty key, or a non-empty value of an
+ *                 Insert, reaches outside [0, keys_bytes) / [0, vals_bytes).
+ *                 *bad_index = the first such command in batch order.  A
+ *                 Remove's val_off and vlen are not looked at.
+ *   LSMCK_ENOSPC  cap is smaller than the encoded size; *img_bytes = the
+ *                 size needed.
+ * On either error no byte of img is written. */
+typedef struct {
+  uint64_t key_off;    /* key   = keys[key_off .. key_off + klen) */
+  uint64_t val_off;    /* value = vals[val_off .. val_off + vlen); ignored for Remove */
+  uint32_t klen, vlen; /* vlen ignored (taken as 0) for Remove */
+  uint32_t type;       /* 1 Insert, 2 Remove */
+  uint32_t reserved;   /* 0 */
+} lsmck_wal_cmd;       /* 32 bytes */
+int lsmck_wal_encode_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes, const uint8_t* vals,
+                           size_t vals_bytes, const lsmck_wal_cmd* cmds, size_t n, uint8_t* img, size_t cap,
+                           size_t* img_bytes, uint64_t* rec_off, uint64_t* bad_index, unsigned flags);
+
+/* Host helper, no GPU: the bytes a batch encodes to (the sum of 13 + klen +
+ * vlen per Insert and 9 + klen per Remove), or UINT64_MAX when a command is
+ * invalid by itself (its type, or klen + vlen > 2^32-1 for an Insert). */
+uint64_t lsmck_wal_encoded_size(const lsmck_wal_cmd* cmds, size_t n);
 
 /* Whole-tree SSTable verify: the batch form of Checksums::verify over many
  * tables (Db::load, src/tokio/db.rs:37-59 -> src/tokio/sstable.rs:34).

@@ -13,6 +13,8 @@ torch already loaded (one HIP runtime per process).  ``load()`` checks that.
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblsmck.so")
 
@@ -22,6 +24,7 @@ ENOMEM = -12
 EIO = -5
 ENODEV = -19
 EHIP = -1000
+ENOSPC = -28  # lsmck_wal_encode_batch: the image buffer is too small
 EJSON = -74
 DATA_MISMATCH = 1
 INDEX_MISMATCH = 2
@@ -63,6 +66,18 @@ class WalRec16(C.Structure):
 
 
 WAL_REC16_REMOVE = 1 << 63
+
+
+class WalCmd(C.Structure):
+    """lsmck_wal_cmd: one command of lsmck_wal_encode_batch (key / value ranges in the arenas)."""
+    _fields_ = [("key_off", C.c_uint64), ("val_off", C.c_uint64), ("klen", C.c_uint32), ("vlen", C.c_uint32),
+                ("type", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# include/lsmck.h lsmck_wal_cmd (32 bytes, no padding)
+WAL_CMD_DTYPE = np.dtype([("key_off", "<u8"), ("val_off", "<u8"), ("klen", "<u4"), ("vlen", "<u4"),
+                          ("type", "<u4"), ("reserved", "<u4")])
+assert WAL_CMD_DTYPE.itemsize == C.sizeof(WalCmd) == 32
 
 
 class TreeReport(C.Structure):
@@ -113,6 +128,9 @@ SIGNATURES = [
     ("lsmck_wal_replay_verify16", C.c_int,
      [vp, vp, sz, C.c_uint, vp, sz, C.POINTER(sz), u64p, u32p, u32p]),  # recs: lsmck_wal_rec16[cap]
     ("lsmck_wal_frame_insert_device", C.c_int, [vp, vp, vp, vp, vp, sz, C.c_uint32, vp]),
+    ("lsmck_wal_encode_batch", C.c_int,
+     [vp, vp, sz, vp, sz, vp, sz, vp, sz, C.POINTER(sz), vp, u64p, C.c_uint]),  # cmds: lsmck_wal_cmd[n]
+    ("lsmck_wal_encoded_size", C.c_uint64, [vp, sz]),
     ("lsmck_checksums_verify_many", C.c_int,
      [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), sz, C.POINTER(C.c_int)]),
     ("lsmck_tree_verify", C.c_int, [vp, C.c_char_p, C.POINTER(TreeReport)]),
@@ -184,7 +202,6 @@ def check(rc, what=""):
 
 def buf_ptr(b):
     """Pointer to a bytes-like object's memory without copying where possible."""
-    import numpy as np
     if isinstance(b, np.ndarray):
         return b.ctypes.data
     if isinstance(b, (bytes, bytearray, memoryview)):

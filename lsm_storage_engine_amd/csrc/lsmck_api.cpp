@@ -406,6 +406,26 @@ struct lsmck_ctx {
     uint32_t* scode0 = nullptr;
     size_t cap_seg0 = 0;
   } wd;
+  // batch WAL encode (lsmck_wal_encode_batch; grow-only, under mu): the
+  // record offsets (n + 1) and the scan's block sums; host form: the uploaded
+  // arenas and commands, and the image
+  struct {
+    uint64_t* off = nullptr;
+    size_t cap_off = 0;
+    uint64_t* bsum = nullptr;
+    size_t cap_bsum = 0;
+    uint8_t* keys = nullptr;
+    size_t cap_keys = 0;
+    uint8_t* vals = nullptr;
+    size_t cap_vals = 0;
+    lsmck_wal_cmd* cmds = nullptr;
+    size_t cap_cmds = 0;
+    uint8_t* img = nullptr;
+    size_t cap_img = 0;
+  } enc;
+  bool enc_time = false;        // option "wal_encode_time": the encode's stages between device events
+  long enc_ns[4] = {0, 0, 0, 0};  // the last timed encode: scan, gather, CRC pass (descriptors included), stamp
+  hipEvent_t enc_ev[6] = {};    // (created by the first timed encode)
   bool wal_recs_direct = false;  // this replay's records go by DMA into the caller's pinned array (under wal_mu)
   bool wal_compact = false;      // this replay's records are lsmck_wal_rec16 (under wal_mu)
   // LSMCK_RECS_DEVICE (under wal_mu): the caller's device array and its capacity
@@ -1260,6 +1280,12 @@ int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value) {
                    (value == 0 ? kVariantNoStream : value == 2 ? kVariantStreamOnly : 0);
     return 0;
   }
+  if (!strcmp(key, "wal_encode_time")) {  // diagnostic: lsmck_wal_encode_batch's stages between device events
+    if (value != 0 && value != 1) return lsmck_host::set_error(LSMCK_EINVAL, "wal_encode_time must be 0 or 1");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->enc_time = value != 0;
+    return 0;
+  }
   return lsmck_host::set_error(LSMCK_EINVAL, "unknown option");
 }
 
@@ -1284,6 +1310,16 @@ int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value) {
     *value = ctx->numa_node;
   } else if (!strcmp(key, "stage_numa_node")) {
     *value = ctx->pin_node;
+  } else if (!strcmp(key, "wal_encode_tile")) {  // lsmck_wal_encode_batch: image bytes per workgroup of the gather
+    *value = (long)lsmk_wal_encode_tile();
+  } else if (!strcmp(key, "wal_encode_scan_ns")) {  // the last timed encode's stages ("wal_encode_time")
+    *value = ctx->enc_ns[0];
+  } else if (!strcmp(key, "wal_encode_gather_ns")) {
+    *value = ctx->enc_ns[1];
+  } else if (!strcmp(key, "wal_encode_crc_ns")) {
+    *value = ctx->enc_ns[2];
+  } else if (!strcmp(key, "wal_encode_stamp_ns")) {
+    *value = ctx->enc_ns[3];
   } else {
     return lsmck_host::set_error(LSMCK_EINVAL, "unknown stat");
   }
@@ -1319,6 +1355,11 @@ void lsmck_ctx_destroy(lsmck_ctx* ctx) {
     if (p) (void)hipFree(p);
   for (void* p : {(void*)ctx->h_woff, (void*)ctx->h_wlen, (void*)ctx->h_wexp})
     if (p) host_free(p);
+  for (void* p : {(void*)ctx->enc.off, (void*)ctx->enc.bsum, (void*)ctx->enc.keys, (void*)ctx->enc.vals,
+                  (void*)ctx->enc.cmds, (void*)ctx->enc.img})
+    if (p) (void)hipFree(p);
+  for (hipEvent_t e : ctx->enc_ev)
+    if (e) (void)hipEventDestroy(e);
   if (ctx->h_verify) host_free(ctx->h_verify);
   if (ctx->h_wrecs) host_free(ctx->h_wrecs);
   if (ctx->wd.recs16) (void)hipFree(ctx->wd.recs16);
@@ -2481,6 +2522,94 @@ int lsmck_wal_frame_insert_device(lsmck_ctx* ctx, uint8_t* img, const uint64_t* 
   DevGuard g(ctx->dev);
   rc = lsmk_wal_frame_insert(img, off, len, crc, n, kmax, pick_stream(ctx, stream));
   return rc ? launch_rc(rc, "wal frame kernel") : 0;
+}
+
+int lsmck_wal_encode_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes, const uint8_t* vals,
+                           size_t vals_bytes, const lsmck_wal_cmd* cmds, size_t n, uint8_t* img, size_t cap,
+                           size_t* img_bytes, uint64_t* rec_off, uint64_t* bad_index, unsigned flags) {
+  int rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!img_bytes) return lsmck_host::set_error(LSMCK_EINVAL, "null img_bytes");
+  *img_bytes = 0;
+  if (flags & ~(LSMCK_DEVICE | LSMCK_HOST_PINNED)) return lsmck_host::set_error(LSMCK_EINVAL, "wal encode: unknown flag");
+  if (n == 0) return 0;
+  if (!cmds) return lsmck_host::set_error(LSMCK_EINVAL, "null commands");
+  if (n >= (1ull << 32)) return lsmck_host::set_error(LSMCK_EINVAL, "more than 2^32-1 commands in one batch");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DevGuard g(ctx->dev);
+  const hipStream_t st = ctx->stream0;
+  ScratchOrder so(ctx, st);
+  if (so.e != hipSuccess) return hip_error(so.e, "hipStreamWaitEvent(scratch)");
+  auto& E = ctx->enc;
+  const bool dev = (flags & LSMCK_DEVICE) != 0;
+  const uint8_t *dk = keys, *dv = vals;
+  const lsmck_wal_cmd* dc = cmds;
+  if (!dev) {  // staged whole: the arenas (once when they are one buffer) and the commands
+    const bool same = keys == vals && keys_bytes == vals_bytes;
+    if ((rc = ensure_dev(&E.keys, &E.cap_keys, keys_bytes)) || (rc = ensure_dev(&E.cmds, &E.cap_cmds, n)) ||
+        (!same && (rc = ensure_dev(&E.vals, &E.cap_vals, vals_bytes))))
+      return rc;
+    if (keys_bytes) HIPCHK(hipMemcpyAsync(E.keys, keys, keys_bytes, hipMemcpyHostToDevice, st));
+    if (!same && vals_bytes) HIPCHK(hipMemcpyAsync(E.vals, vals, vals_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(E.cmds, cmds, n * sizeof(lsmck_wal_cmd), hipMemcpyHostToDevice, st));
+    dk = E.keys;
+    dv = same ? E.keys : E.vals;
+    dc = E.cmds;
+  }
+  if ((rc = ensure_dev(&E.off, &E.cap_off, n + 1)) ||
+      (rc = ensure_dev(&E.bsum, &E.cap_bsum, (size_t)lsmk_wal_encode_scan_blocks(n) + 1)))
+    return rc;
+  // 1. sizes, validation, offsets; the total and the first invalid command come back
+  unsigned long long* info = ctx->d_verify + 2;
+  HIPCHK(hipMemsetAsync(info, 0xFF, 16, st));
+  const bool timed = ctx->enc_time;
+  hipEvent_t* ev = ctx->enc_ev;
+  if (timed && !ev[0])
+    for (int k = 0; k < 6; ++k) HIPCHK(hipEventCreate(&ev[k]));
+  if (timed) HIPCHK(hipEventRecord(ev[0], st));
+  if ((rc = lsmk_wal_encode_scan(dc, n, keys_bytes, vals_bytes, E.off, E.bsum, info, st)))
+    return launch_rc(rc, "wal encode scan kernels");
+  if (timed) HIPCHK(hipEventRecord(ev[1], st));
+  HIPCHK(hipMemcpyAsync(ctx->h_verify + 2, info, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const uint64_t bad = ctx->h_verify[2], total = ctx->h_verify[3];
+  if (bad != ~0ull) {
+    if (bad_index) *bad_index = bad;
+    return lsmck_host::set_error(LSMCK_EINVAL, "wal encode: invalid command (type, lengths or source range)");
+  }
+  *img_bytes = (size_t)total;
+  if (cap < total) return lsmck_host::set_error(LSMCK_ENOSPC, "wal encode: the image buffer is too small");
+  uint8_t* di = img;
+  if (!dev) {
+    if ((rc = ensure_dev(&E.img, &E.cap_img, (size_t)total))) return rc;
+    di = E.img;
+  }
+  if ((rc = ensure_dev(&ctx->d_woff, &ctx->cap_woff, n)) || (rc = ensure_dev(&ctx->d_wlen, &ctx->cap_wlen, n)) ||
+      (rc = ensure_dev(&ctx->d_vcrc, &ctx->cap_vcrc, n)))
+    return rc;
+  // 2. gather  3. payload CRCs over the image  4. stamp
+  if (timed) HIPCHK(hipEventRecord(ev[2], st));
+  if ((rc = lsmk_wal_encode_gather(dk, dv, dc, n, E.off, di, total, st))) return launch_rc(rc, "wal encode gather kernel");
+  if (timed) HIPCHK(hipEventRecord(ev[3], st));
+  if ((rc = lsmk_wal_encode_desc(dc, n, E.off, ctx->d_woff, ctx->d_wlen, st)))
+    return launch_rc(rc, "wal encode descriptor kernel");
+  if ((rc = crc_desc_device(ctx, ctx->scratch, di, ctx->d_woff, ctx->d_wlen, n, ctx->d_vcrc, st))) return rc;
+  if (timed) HIPCHK(hipEventRecord(ev[4], st));
+  if ((rc = lsmk_wal_encode_stamp(di, E.off, ctx->d_vcrc, n, st))) return launch_rc(rc, "wal encode stamp kernel");
+  if (timed) HIPCHK(hipEventRecord(ev[5], st));
+  if (rec_off)
+    HIPCHK(hipMemcpyAsync(rec_off, E.off, n * 8, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  if (!dev) HIPCHK(hipMemcpyAsync(img, di, (size_t)total, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (timed) {
+    const int pair[4][2] = {{0, 1}, {2, 3}, {3, 4}, {4, 5}};
+    for (int k = 0; k < 4; ++k) {
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, ev[pair[k][0]], ev[pair[k][1]]));
+      ctx->enc_ns[k] = (long)((double)ms * 1e6);
+    }
+  }
+  return 0;
 }
 
 }  // extern "C"

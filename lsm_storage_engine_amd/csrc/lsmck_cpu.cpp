@@ -444,6 +444,18 @@ size_t lsmck_wal_encode_remove(const uint8_t* key, uint32_t klen, uint8_t* out) 
   return 9 + (size_t)klen;
 }
 
+uint64_t lsmck_wal_encoded_size(const lsmck_wal_cmd* cmds, size_t n) {
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const lsmck_wal_cmd& c = cmds[i];
+    if (c.type != 1 && c.type != 2) return UINT64_MAX;
+    const uint64_t vlen = c.type == 1 ? c.vlen : 0;
+    if ((uint64_t)c.klen + vlen > 0xFFFFFFFFull) return UINT64_MAX;
+    total += (uint64_t)(c.type == 1 ? 13u : 9u) + c.klen + vlen;  // (widened first: klen alone may be 2^32-1)
+  }
+  return total;
+}
+
 void lsmck_gen_zipf_lengths(uint64_t seed, double s, int kmax, uint32_t lmin, size_t n, uint32_t* out) {
   lsmck_host::gen_zipf_lengths(seed, s, kmax, lmin, 0, n, out);
 }

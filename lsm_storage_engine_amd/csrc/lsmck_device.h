@@ -88,6 +88,23 @@ int lsmk_wal_chain(const uint8_t* img, uint64_t n, const uint64_t* bits, const u
                    uint64_t w1, uint64_t start, uint64_t lim, hipStream_t st);
 int lsmk_wal_frame_insert(uint8_t* img, const uint64_t* off, const uint32_t* len, const uint32_t* crc, uint64_t n,
                           uint32_t kmax, hipStream_t st);
+// batch WAL encode (lsmck_wal_encode_batch; lsmck_wal.hip wal_encode_*)
+static_assert(sizeof(lsmck_wal_cmd) == 32, "lsmck_wal_cmd is 32 bytes");
+uint32_t lsmk_wal_encode_tile(void);            // the gather's tile bytes
+uint64_t lsmk_wal_encode_scan_blocks(uint64_t n);  // bsum entries of the offset scan
+// sizes, validation and the exclusive scan: off[0..n] (off[n] = the total);
+// info[0] = the first invalid command (atomic min; the caller sets it to ~0),
+// info[1] = the total
+int lsmk_wal_encode_scan(const lsmck_wal_cmd* cmds, uint64_t n, uint64_t keys_bytes, uint64_t vals_bytes,
+                         uint64_t* off, uint64_t* bsum, unsigned long long* info, hipStream_t st);
+// the image but its CRC fields (zero bytes) from the arenas and the commands
+int lsmk_wal_encode_gather(const uint8_t* keys, const uint8_t* vals, const lsmck_wal_cmd* cmds, uint64_t n,
+                           const uint64_t* off, uint8_t* img, uint64_t total, hipStream_t st);
+// payload descriptors for the CRC batch
+int lsmk_wal_encode_desc(const lsmck_wal_cmd* cmds, uint64_t n, const uint64_t* off, uint64_t* poff, uint32_t* plen,
+                         hipStream_t st);
+// the records' CRC fields
+int lsmk_wal_encode_stamp(uint8_t* img, const uint64_t* off, const uint32_t* crc, uint64_t n, hipStream_t st);
 int lsmk_wal_emit(const uint8_t* img, uint64_t n, const uint32_t* chain, const uint64_t* pos,
                   const unsigned long long* info, uint32_t m, lsmck_wal_rec* recs, uint64_t* poff, uint32_t* plen,
                   uint32_t* pcrc, hipStream_t st);

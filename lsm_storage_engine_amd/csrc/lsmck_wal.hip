@@ -37,6 +37,7 @@ __device__ uint64_t g_seg_clock[3 * 131072];
 #include "lsmck.h"
 #include "lsmck_device.h"
 #include "lsmck_segwalk.h"
+#include "lsmck_walenc.h"
 
 namespace lsmck {
 
@@ -697,11 +698,180 @@ __global__ __launch_bounds__(256) void wal_recs_compact(const lsmck_wal_rec* __r
   }
 }
 
+// --- batch WAL encode (lsmck_wal_encode_batch) ------------------------------
+// The batch form of CommandLog::log (wal.rs:165-196): commands (key and value
+// ranges in two arenas) -> the log image.
+//   1. wal_encode_scan_*: every command's record size (13 + klen + vlen, or
+//      9 + klen) and validity, the exclusive u64 scan of the sizes (the three
+//      passes of wal_seg_scan_*; pass b is that file's) -> off[0..n];
+//   2. wal_encode_gather: the image but its CRC fields, output-centric;
+//   3. wal_encode_desc + the CRC batch over the image's payloads;
+//   4. wal_encode_stamp: the CRC fields.
+// The record arithmetic and the gather's tile logic: lsmck_walenc.h.
+
+__global__ __launch_bounds__(SSCAN_BLOCK) void wal_encode_scan_a(const lsmck_wal_cmd* __restrict__ cmds, uint64_t n,
+                                                                   uint64_t kb, uint64_t vb,
+                                                                   uint64_t* __restrict__ bsum,
+                                                                   unsigned long long* __restrict__ info) {
+  __shared__ uint64_t s[SSCAN_BLOCK / 64];
+  const uint64_t i0 = ((uint64_t)blockIdx.x * SSCAN_BLOCK + threadIdx.x) * SSCAN_ITEMS;
+  uint64_t x = 0, bad = ~0ull;
+  for (uint32_t j = 0; j < SSCAN_ITEMS; ++j)
+    if (i0 + j < n) {
+      const uint64_t sz = enc::rec_size(cmds[i0 + j], kb, vb);
+      if (!sz && bad == ~0ull) bad = i0 + j;
+      x += sz;
+    }
+  if (bad != ~0ull) atomicMin(info, (unsigned long long)bad);  // the first invalid command in batch order
+  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
+  if ((threadIdx.x & 63u) == 0) s[threadIdx.x >> 6] = x;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint64_t t = 0;
+    for (uint32_t k = 0; k < SSCAN_BLOCK / 64; ++k) t += s[k];
+    bsum[blockIdx.x] = t;
+  }
+}
+__global__ __launch_bounds__(SSCAN_BLOCK) void wal_encode_scan_c(const lsmck_wal_cmd* __restrict__ cmds, uint64_t n,
+                                                                   uint64_t kb, uint64_t vb,
+                                                                   const uint64_t* __restrict__ bsum,
+                                                                   uint64_t* __restrict__ off,
+                                                                   unsigned long long* __restrict__ info) {
+  __shared__ uint64_t s[SSCAN_BLOCK / 64];
+  const uint64_t i0 = ((uint64_t)blockIdx.x * SSCAN_BLOCK + threadIdx.x) * SSCAN_ITEMS;
+  uint64_t v[SSCAN_ITEMS], x = 0;
+  for (uint32_t j = 0; j < SSCAN_ITEMS; ++j) {
+    v[j] = i0 + j < n ? enc::rec_size(cmds[i0 + j], kb, vb) : 0ull;
+    x += v[j];
+  }
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t inc = wave_incl_scan(x, lane);
+  if (lane == 63u) s[threadIdx.x >> 6] = inc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint64_t acc = 0;
+    for (uint32_t k = 0; k < SSCAN_BLOCK / 64; ++k) {
+      const uint64_t t = s[k];
+      s[k] = acc;
+      acc += t;
+    }
+  }
+  __syncthreads();
+  uint64_t run = bsum[blockIdx.x] + s[threadIdx.x >> 6] + inc - x;
+  for (uint32_t j = 0; j < SSCAN_ITEMS; ++j)
+    if (i0 + j <= n) {  // (off[n]: the total)
+      off[i0 + j] = run;
+      if (i0 + j == n) info[1] = run;
+      run += v[j];
+    }
+}
+
+// The gather (lsmck_walenc.h): a workgroup per tile, 256 consecutive chunks
+// per pass of the block.  The tile's first record comes from the search of
+// off[] by the whole wave, made by each of the four waves for itself (the
+// same loads: no hand-over through LDS); the offsets of the records that
+// start inside the tile then go to LDS, relative to the tile (u16), a block's
+// load at a time until one ends past the tile, and with them the commands of
+// the tile's first 256 records; every lane finds its chunks' records there,
+// kGroup chunks at a time (enc::chunks).
+__global__ __launch_bounds__(enc::kBlock) void wal_encode_gather(const uint8_t* __restrict__ keys,
+                                                                  const uint8_t* __restrict__ vals,
+                                                                  const lsmck_wal_cmd* __restrict__ cmds, uint64_t n,
+                                                                  const uint64_t* __restrict__ off,
+                                                                  uint8_t* __restrict__ img) {
+  __shared__ enc::slice_t srel[enc::kSlice + 1u];
+  __shared__ lsmck_wal_cmd cache[enc::kCache];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  enc::Tile t;
+  t.keys = keys;
+  t.vals = vals;
+  t.cmds = cmds;
+  t.total = (int64_t)off[n];
+  // (the first tile starts at or before the image: ts <= 0)
+  t.ts = (int64_t)blockIdx.x * enc::kTile - (int64_t)((uintptr_t)img & (enc::kTile - 1u));
+  const int64_t t0 = t.ts > 0 ? t.ts : 0;
+  uint64_t lo = 0, hi = n;  // off[0] = 0 <= t0 < total = off[n]
+  while (hi - lo > 1) {     // (wave-uniform)
+    const uint64_t idx = enc::probe(lo, hi, lane);
+    const bool le = idx < hi && (int64_t)off[idx] <= t0;
+    enc::narrow(lo, hi, (uint32_t)__popcll(__ballot(le)));
+  }
+  t.r0 = lo;
+  t.off0 = (int64_t)off[lo];
+  if (tid == 0) srel[0] = 0;
+  if (t.r0 + tid < n) cache[tid] = cmds[t.r0 + tid];
+  t.N = 1;
+  for (uint32_t base = 0; base < enc::kSlice; base += enc::kBlock) {
+    const uint32_t v = enc::slice_entry(off, n, t.r0, 1u + base + tid, t.ts);
+    srel[1u + base + tid] = (enc::slice_t)v;
+    t.N += enc::kBlock;
+    if (!__syncthreads_or(tid == enc::kBlock - 1u && v < enc::kTile)) break;  // (the load's last entry is past the tile)
+  }
+  for (uint32_t p = tid * 16u; p < enc::kTile; p += enc::kGroup * enc::kBlock * 16u)
+    enc::chunks(t, (const enc::slice_t*)srel, (const lsmck_wal_cmd*)cache, p, enc::kBlock * 16u, img);
+}
+
+// payload descriptors for the CRC batch (enc::payload_desc); a thread per record
+__global__ __launch_bounds__(256) void wal_encode_desc(const lsmck_wal_cmd* __restrict__ cmds, uint64_t n,
+                                                        const uint64_t* __restrict__ off, uint64_t* __restrict__ poff,
+                                                        uint32_t* __restrict__ plen) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t len;
+  poff[i] = enc::payload_desc(cmds, off, i, &len);
+  plen[i] = len;
+}
+
+// the CRC fields (byte stores: headers start at any offset); a thread per record
+__global__ __launch_bounds__(256) void wal_encode_stamp(uint8_t* __restrict__ img, const uint64_t* __restrict__ off,
+                                                         const uint32_t* __restrict__ crc, uint64_t n) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint8_t* h = img + off[i];
+  const uint32_t c = crc[i];
+  for (int b = 0; b < 4; ++b) h[1 + b] = (uint8_t)(c >> (8 * b));
+}
+
 }  // namespace lsmck
 
 using namespace lsmck;
 
 static int launch_err();
+
+extern "C" uint32_t lsmk_wal_encode_tile(void) { return enc::kTile; }
+extern "C" uint64_t lsmk_wal_encode_scan_blocks(uint64_t n) {
+  return (n + 1 + SSCAN_BLOCK * SSCAN_ITEMS - 1) / (SSCAN_BLOCK * SSCAN_ITEMS);
+}
+extern "C" int lsmk_wal_encode_scan(const lsmck_wal_cmd* cmds, uint64_t n, uint64_t keys_bytes, uint64_t vals_bytes,
+                                    uint64_t* off, uint64_t* bsum, unsigned long long* info, hipStream_t st) {
+  const uint32_t nb = (uint32_t)lsmk_wal_encode_scan_blocks(n);
+  hipLaunchKernelGGL(wal_encode_scan_a, dim3(nb), dim3(SSCAN_BLOCK), 0, st, cmds, n, keys_bytes, vals_bytes, bsum,
+                     info);
+  hipLaunchKernelGGL(wal_seg_scan_b, dim3(1), dim3(1024), 0, st, bsum, nb);
+  hipLaunchKernelGGL(wal_encode_scan_c, dim3(nb), dim3(SSCAN_BLOCK), 0, st, cmds, n, keys_bytes, vals_bytes,
+                     (const uint64_t*)bsum, off, info);
+  return launch_err();
+}
+extern "C" int lsmk_wal_encode_gather(const uint8_t* keys, const uint8_t* vals, const lsmck_wal_cmd* cmds, uint64_t n,
+                                      const uint64_t* off, uint8_t* img, uint64_t total, hipStream_t st) {
+  if (n == 0 || total == 0) return 0;
+  const uint64_t tiles = (((uintptr_t)img & (enc::kTile - 1u)) + total + enc::kTile - 1u) / enc::kTile;
+  if (tiles > 0x7FFFFFFFull) return -(int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(wal_encode_gather, dim3((unsigned)tiles), dim3(enc::kBlock), 0, st, keys, vals, cmds, n, off, img);
+  return launch_err();
+}
+extern "C" int lsmk_wal_encode_desc(const lsmck_wal_cmd* cmds, uint64_t n, const uint64_t* off, uint64_t* poff,
+                                    uint32_t* plen, hipStream_t st) {
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(wal_encode_desc, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cmds, n, off, poff, plen);
+  return launch_err();
+}
+extern "C" int lsmk_wal_encode_stamp(uint8_t* img, const uint64_t* off, const uint32_t* crc, uint64_t n,
+                                     hipStream_t st) {
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(wal_encode_stamp, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, img, off, crc, n);
+  return launch_err();
+}
 
 // Segment bytes for a walk over `len` bytes: a power of two from 512 B to
 // 16 MiB giving about 2^16 segments (one thread each; same-box sweeps, profiles/r04/j:

@@ -92,6 +92,17 @@ class _PinnedRecords:
                                     "descr": dtype.descr, "version": 3}
 
 
+class WalEncodeError(_lib.LsmckError):
+    """lsmck_wal_encode_batch refused the batch: ``bad_index`` is the first
+    invalid command (LSMCK_EINVAL), or ``needed`` the image's size when the
+    buffer given is smaller (LSMCK_ENOSPC); the other one is None."""
+
+    def __init__(self, rc, what, bad_index=None, needed=None):
+        self.bad_index = bad_index
+        self.needed = needed
+        super().__init__(rc, f"{what} (bad_index={bad_index}, needed={needed})")
+
+
 class Context:
     def __init__(self, device=0):
         lib = _lib.load()
@@ -261,6 +272,49 @@ class Context:
         of a device-resident log (all device pointers)."""
         _lib.check(self.lib.lsmck_wal_frame_insert_device(self.handle, img_ptr, off_ptr, len_ptr, crc_ptr, n, kmax,
                                                            stream), "wal_frame_insert_device")
+
+    def _wal_encode(self, keys, kb, vals, vb, cmds, n, img, cap, rec_off, flags):
+        none = 2 ** 64 - 1
+        nbytes, bad = C.c_size_t(), C.c_uint64(none)
+        rc = self.lib.lsmck_wal_encode_batch(self.handle, keys, kb, vals, vb, cmds, n, img, cap, C.byref(nbytes),
+                                             rec_off, C.byref(bad), flags)
+        if rc == _lib.EINVAL and bad.value != none:
+            raise WalEncodeError(rc, "wal_encode_batch", bad_index=bad.value)
+        if rc == _lib.ENOSPC:
+            raise WalEncodeError(rc, "wal_encode_batch", needed=nbytes.value)
+        _lib.check(rc, "wal_encode_batch")
+        return nbytes.value
+
+    def wal_encode_batch(self, keys, vals, cmds, pinned=False):
+        """lsmck_wal_encode_batch, host form: the log image of the commands
+        ``cmds`` (WAL_CMD_DTYPE: key / value ranges in the uint8 arenas
+        ``keys`` / ``vals``, which may be one array), encoded on the GPU.
+        Returns (image: np.uint8 array, rec_off: np.uint64 array of the
+        records' header offsets).  Raises WalEncodeError (``bad_index``: the
+        first invalid command)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint8)
+        vals = keys if vals is keys else np.ascontiguousarray(vals, dtype=np.uint8)
+        cmds = np.ascontiguousarray(cmds, dtype=_lib.WAL_CMD_DTYPE)
+        n = len(cmds)
+        size = self.lib.lsmck_wal_encoded_size(cmds.ctypes.data, n)
+        if size == 2 ** 64 - 1:
+            size = 0  # (the call reports the first invalid command)
+        img = np.empty(size, dtype=np.uint8)
+        rec_off = np.empty(n, dtype=np.uint64)
+        flags = _lib.HOST_PINNED if pinned else _lib.HOST
+        got = self._wal_encode(keys.ctypes.data, keys.nbytes, vals.ctypes.data, vals.nbytes, cmds.ctypes.data, n,
+                               img.ctypes.data, size, rec_off.ctypes.data, flags)
+        assert got == size
+        return img, rec_off
+
+    def wal_encode_batch_device(self, keys_ptr, keys_bytes, vals_ptr, vals_bytes, cmds_ptr, n, img_ptr, cap,
+                                rec_off_ptr=None):
+        """lsmck_wal_encode_batch on device pointers (cmds: n lsmck_wal_cmd;
+        rec_off_ptr: n u64 or None).  Returns the image's bytes; raises
+        WalEncodeError with ``bad_index`` (an invalid command) or ``needed``
+        (cap is smaller than the encoded size); nothing was written then."""
+        return self._wal_encode(keys_ptr, keys_bytes, vals_ptr, vals_bytes, cmds_ptr, n, img_ptr, cap, rec_off_ptr,
+                                _lib.DEVICE)
 
     def wal_replay_verify(self, image, device_ptr=None, cap=None, pinned_recs=False, compact=False):
         """Returns (records, status, (bad_index, bad_crc, bad_expected)).

@@ -17,6 +17,8 @@ import os
 import struct
 from dataclasses import dataclass
 
+import numpy as np
+
 from . import _lib
 from .crc32 import checksum_ieee
 
@@ -120,6 +122,20 @@ class CommandLog:
         self.file.flush()
         return len(record.key) + 5
 
+    def log_batch(self, records, ctx):
+        """The batch form of ``log`` (a group commit): the records' arenas and
+        commands are built here, the image is encoded in one GPU batch
+        (lsmck_wal_encode_batch) and appended with one write and flush.
+        Returns the list of the values ``log`` returns per record; the file
+        ends up as ``for r in records: self.log(r)`` leaves it."""
+        cmds, out = encode_commands(records)
+        keys = np.frombuffer(b"".join(r.key for r in records), dtype=np.uint8)
+        vals = np.frombuffer(b"".join(r.val for r in records if isinstance(r, Insert)), dtype=np.uint8)
+        img, _ = ctx.wal_encode_batch(keys, vals, cmds)
+        self.file.write(img.tobytes())
+        self.file.flush()
+        return out
+
     # --- replay -----------------------------------------------------------
     def _read_exact(self, n):
         b = self.file.read(n)
@@ -191,6 +207,22 @@ class CommandLog:
             consumed = k0 + len(data)
         self.file.seek(pos + consumed)
         return out
+
+
+def encode_commands(records):
+    """lsmck_wal_cmd entries (WAL_CMD_DTYPE) for a sequence of Insert / Remove
+    whose keys lie back to back in one arena and whose values in another, in
+    record order; and the values ``CommandLog.log`` returns for them."""
+    n = len(records)
+    cmds = np.zeros(n, dtype=_lib.WAL_CMD_DTYPE)
+    ins = np.fromiter((isinstance(r, Insert) for r in records), dtype=bool, count=n)
+    klen = np.fromiter((len(r.key) for r in records), dtype=np.uint64, count=n)
+    vlen = np.fromiter((len(r.val) if i else 0 for r, i in zip(records, ins)), dtype=np.uint64, count=n)
+    cmds["klen"], cmds["vlen"] = klen, vlen
+    cmds["key_off"] = np.cumsum(klen) - klen
+    cmds["val_off"] = np.cumsum(vlen) - vlen
+    cmds["type"] = np.where(ins, INSERT, REMOVE)
+    return cmds, (klen + vlen + np.uint64(5)).tolist()
 
 
 def _split_off_msg(at, length):

@@ -3,7 +3,7 @@
 # which stay in git history up to d60fa90).  Run as
 #   gpurun -- 'ROUND=r06a STEPS="smoke tests" TESTS=tests/test_gpu_wal_lengths.py bash tools/gpu_run.sh'
 # Steps picked by STEPS (space list), run in this order:
-#   build smoke tests pytest bench benchkt c3pmc walbig walbigkt walmib wallogs waldiag sha shaab tree server
+#   build smoke tests pytest bench benchkt c3pmc walbig walbigkt walmib wallogs waldiag encbig encbigkt sha shaab tree server
 #   custom (runs $CUSTOM under the same time limit / stop rules)
 # Logs go to gpurun_out/$ROUND/<step>.log.  A test failure goes on to the next
 # step; a timeout / abort / crash (rc 124, 137, 134, 139, > 128) ends the call.
@@ -59,6 +59,12 @@ if has waldiag; then
   step waldiag 300 python3 -u tools/wal_diag.py
   step waldiagkt 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_waldev -o kt -- python3 tools/wal_kt.py
   python3 tools/kt_stats.py $O/kt_waldev > $O/kt_stats_waldev.txt 2>&1
+fi
+# the batch WAL encode at config 3's scale (2^24 commands, ~24 GiB): stages, the D2D copy yardstick; then its kernel trace
+has encbig && step encbig 300 python3 -u tools/wal_encode_big.py --reps 5 ${ENCBIG_ARGS}
+if has encbigkt; then
+  step encbigkt 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_encbig -o kt -- python3 tools/wal_encode_big.py --reps 2 --copy 0 ${ENCBIG_ARGS}
+  python3 tools/kt_stats.py $O/kt_encbig > $O/kt_stats_encbig.txt 2>&1
 fi
 has sha && step sha 400 python3 bench.py --full --digest sha256 --steps 5 --warmup 1
 has shaab && step shaab 600 python3 bench.py --digest sha256 --variants=${SHA_VARIANTS:--,t6,t16} --rounds 3 --steps 3 --warmup 1 --no-cpu-baseline --no-host-roundtrip --no-config4
