@@ -44,7 +44,7 @@ extern "C" {
 #define LSMCK_ENOMEM (-12)
 #define LSMCK_EIO (-5)
 #define LSMCK_ENODEV (-19)
-#define LSMCK_ENOSPC (-28) /* lsmck_wal_encode_batch: the image buffer is too small */
+#define LSMCK_ENOSPC (-28) /* lsmck_wal_encode_batch, lsmck_sstable_encode_batch: an output buffer is too small */
 #define LSMCK_EHIP (-1000) /* LSMCK_EHIP - hipError_t */
 
 /* flags for batch calls */
@@ -281,6 +281,10 @@ int lsmck_device_count(void);
  *                 1 = lsmck_wal_encode_batch records device events around
  *                 its stages (tools/wal_encode_big.py reads them back as
  *                 stats); 0 = none (default).
+ *   "sst_encode_time"  DIAGNOSTIC, not part of the stable option list, as
+ *                 "wal_encode_time": 1 = lsmck_sstable_encode_batch records
+ *                 device events around its stages (tools/sst_encode_big.py
+ *                 reads them back as stats); 0 = none (default).
  * Returns 0, or LSMCK_EINVAL for an unknown key / value. */
 int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value);
 
@@ -306,6 +310,14 @@ int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value);
  *                    device events, with "wal_encode_time" 1: the size /
  *                    validate / scan kernels, the gather, the descriptors and
  *                    the CRC pass, the stamp.
+ *   "sst_encode_tile"  bytes of the data arena one workgroup of
+ *                    lsmck_sstable_encode_batch's gather kernel writes (a power
+ *                    of two, at most 32 KiB; tiles are aligned on the arena's address).
+ *   "sst_encode_scan_ns", "sst_encode_gather_ns", "sst_encode_index_ns",
+ *   "sst_encode_sha_ns"  DIAGNOSTIC, subject to change: the last lsmck_sstable_encode_batch's
+ *                    stages between device events, with "sst_encode_time" 1:
+ *                    sizes / order / index plan / spans, the data gather, the
+ *                    index writer, the two digest passes.
  * Returns 0 and *value, or LSMCK_EINVAL for an unknown key. */
 int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value);
 
@@ -487,6 +499,73 @@ int lsmck_wal_encode_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_byte
  * vlen per Insert and 9 + klen per Remove), or UINT64_MAX when a command is
  * invalid by itself (its type, or klen + vlen > 2^32-1 for an Insert). */
 uint64_t lsmck_wal_encoded_size(const lsmck_wal_cmd* cmds, size_t n);
+
+/* Batch SSTable encode: the batch form of SsTable::from_memtable's file
+ * writes (src/tokio/sstable.rs:84-129, src/sync/sstable.rs:135-141,241-253)
+ * and of merge_compact's (tokio/sstable.rs:135-192) for a bulk load, a flush
+ * of many memtables or a compaction's output -- the write-side counterpart of
+ * lsmck_checksums_verify_many: many tables encoded and hashed in one call.
+ * Entries reuse lsmck_wal_cmd (type must be 1; a tombstone in the reference
+ * is an ordinary pair whose value is [0]): entry i names its key in the
+ * `keys` arena and its value in the `vals` arena; the arenas may be one
+ * buffer, and source ranges may overlap or repeat.  Table t is entries
+ * [table_first[t], table_first[t+1]) in that order; table_first (always a
+ * HOST pointer, ntab + 1 values) starts at 0, ends at n and does not
+ * decrease.  An empty table is allowed.
+ *   data file of table t  = [u32 klen LE][u32 vlen LE][key][val] over its
+ *     entries (datafile.rs:27-35); the tables' data files lie back to back
+ *     in `data`, in table order, without padding;
+ *   index file of table t = the bincode 1.x fixint image of the reference's
+ *     BTreeMap<Vec<u8>, u64> (sstable_index.rs:42-46): u64 count =
+ *     ceil(m_t / 100), then for every entry i of the table with i % 100 == 0
+ *     u64 klen, the key, u64 pos -- the record's offset in its own table's
+ *     data file; the index files lie back to back in `index` (an empty
+ *     table's is the 8 bytes of a zero count);
+ *   spans[t] (optional) = where table t's two files lie;
+ *   data_sha[32t ..], index_sha[32t ..] = the SHA-256 of table t's data and
+ *     index file (checksums.rs:64-80; the base64 and the JSON stay on the
+ *     host: lsmck_base64_encode).  Either may be NULL: that image is not
+ *     hashed.  One table is one sequential SHA-256 on one GPU lane.
+ * flags: LSMCK_DEVICE -- keys, vals, ents (8-byte aligned), data, index,
+ * spans and the digest arrays are device pointers; LSMCK_HOST (optionally
+ * | LSMCK_HOST_PINNED, a hint only) -- all host pointers, staged whole as
+ * lsmck_wal_encode_batch's host form is, bounded by device memory.  Any other
+ * flag bit is LSMCK_EINVAL.  table_first, data_bytes, index_bytes and
+ * bad_index are host pointers either way.  Synchronous; scratch comes from
+ * the context, so calls on one context serialise.  The sizes and the error
+ * words are read back once, before anything is written.
+ * Returns 0 (n == 0 and ntab == 0: both sizes 0; n == 0 with ntab > 0: ntab
+ * empty tables), or
+ *   LSMCK_EINVAL  with *bad_index = the first offending entry in batch order:
+ *                 its type is not 1; 8 + klen + vlen > 2^32-1 (the reference
+ *                 forms the record size in u32, datafile.rs:34); a non-empty
+ *                 source range lies outside its arena; or the entry is not
+ *                 the first of its table and its key is not strictly greater
+ *                 -- bytewise, a proper prefix first -- than its
+ *                 predecessor's (the reference's memtable is a BTreeMap;
+ *                 order across a table boundary is not checked).
+ *                 With *bad_index = UINT64_MAX: table_first is malformed
+ *                 (checked before any GPU work), n or ntab is 2^32 or more,
+ *                 or a digest is asked for a table whose image is above
+ *                 2^32-1 bytes (lsmck_last_error names the table).
+ *   LSMCK_ENOSPC  data_cap or index_cap is too small; *data_bytes and
+ *                 *index_bytes = the sizes needed.
+ * On any error no byte of data, index, spans or the digest arrays is written. */
+typedef struct {
+  uint64_t data_off, data_len;   /* table t's data file  = data [data_off  .. data_off  + data_len)  */
+  uint64_t index_off, index_len; /* table t's index file = index[index_off .. index_off + index_len) */
+} lsmck_sstable_span;            /* 32 bytes */
+int lsmck_sstable_encode_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes, const uint8_t* vals,
+                               size_t vals_bytes, const lsmck_wal_cmd* ents, size_t n, const uint64_t* table_first,
+                               size_t ntab, uint8_t* data, size_t data_cap, uint8_t* index, size_t index_cap,
+                               lsmck_sstable_span* spans, uint8_t* data_sha, uint8_t* index_sha, size_t* data_bytes,
+                               size_t* index_bytes, uint64_t* bad_index, unsigned flags);
+
+/* Host helper, no GPU: the two arena sizes a batch encodes to.  Returns 0, or
+ * LSMCK_EINVAL when an entry is invalid by itself (its type, or 8 + klen +
+ * vlen > 2^32-1) or table_first is malformed. */
+int lsmck_sstable_encoded_size(const lsmck_wal_cmd* ents, size_t n, const uint64_t* table_first, size_t ntab,
+                               uint64_t* data_bytes, uint64_t* index_bytes);
 
 /* Whole-tree SSTable verify: the batch form of Checksums::verify over many
  * tables (Db::load, src/tokio/db.rs:37-59 -> src/tokio/sstable.rs:34).

@@ -24,7 +24,7 @@ ENOMEM = -12
 EIO = -5
 ENODEV = -19
 EHIP = -1000
-ENOSPC = -28  # lsmck_wal_encode_batch: the image buffer is too small
+ENOSPC = -28  # lsmck_wal_encode_batch, lsmck_sstable_encode_batch: an output buffer is too small
 EJSON = -74
 DATA_MISMATCH = 1
 INDEX_MISMATCH = 2
@@ -80,6 +80,17 @@ WAL_CMD_DTYPE = np.dtype([("key_off", "<u8"), ("val_off", "<u8"), ("klen", "<u4"
 assert WAL_CMD_DTYPE.itemsize == C.sizeof(WalCmd) == 32
 
 
+class SstableSpan(C.Structure):
+    """lsmck_sstable_span: where one table's data and index file lie in lsmck_sstable_encode_batch's arenas."""
+    _fields_ = [("data_off", C.c_uint64), ("data_len", C.c_uint64), ("index_off", C.c_uint64),
+                ("index_len", C.c_uint64)]
+
+
+# include/lsmck.h lsmck_sstable_span (32 bytes, no padding)
+SSTABLE_SPAN_DTYPE = np.dtype([("data_off", "<u8"), ("data_len", "<u8"), ("index_off", "<u8"), ("index_len", "<u8")])
+assert SSTABLE_SPAN_DTYPE.itemsize == C.sizeof(SstableSpan) == 32
+
+
 class TreeReport(C.Structure):
     _fields_ = [("tables", C.c_uint64), ("table_bytes", C.c_uint64), ("bad_tables", C.c_uint64),
                 ("first_index", C.c_uint64), ("first_status", C.c_int), ("reserved", C.c_int),
@@ -131,6 +142,9 @@ SIGNATURES = [
     ("lsmck_wal_encode_batch", C.c_int,
      [vp, vp, sz, vp, sz, vp, sz, vp, sz, C.POINTER(sz), vp, u64p, C.c_uint]),  # cmds: lsmck_wal_cmd[n]
     ("lsmck_wal_encoded_size", C.c_uint64, [vp, sz]),
+    ("lsmck_sstable_encode_batch", C.c_int,  # ents: lsmck_wal_cmd[n]; table_first: host u64[ntab + 1]
+     [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, vp, vp, C.POINTER(sz), C.POINTER(sz), u64p, C.c_uint]),
+    ("lsmck_sstable_encoded_size", C.c_int, [vp, sz, vp, sz, u64p, u64p]),
     ("lsmck_checksums_verify_many", C.c_int,
      [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), sz, C.POINTER(C.c_int)]),
     ("lsmck_tree_verify", C.c_int, [vp, C.c_char_p, C.POINTER(TreeReport)]),

@@ -351,7 +351,7 @@ struct lsmck_ctx {
   std::mutex mu;
   DescScratch scratch;           // device-mode descriptor scratch
   hipEvent_t scratch_ev = nullptr;
-  unsigned long long* d_verify = nullptr;  // [n_bad, first_bad]
+  unsigned long long* d_verify = nullptr;  // [n_bad, first_bad]; [2..3] the WAL encode's, [4..7] the SSTable encode's words
   unsigned long long* h_verify = nullptr;  // pinned
   // device verify / device WAL replay (grow-only; part of the scratch, ordered by scratch_ev)
   uint32_t* d_vcrc = nullptr;  // computed CRCs
@@ -426,6 +426,55 @@ struct lsmck_ctx {
   bool enc_time = false;        // option "wal_encode_time": the encode's stages between device events
   long enc_ns[4] = {0, 0, 0, 0};  // the last timed encode: scan, gather, CRC pass (descriptors included), stamp
   hipEvent_t enc_ev[6] = {};    // (created by the first timed encode)
+  // batch SSTable encode (lsmck_sstable_encode_batch; grow-only, under mu):
+  // the record offsets (n + 1), the scans' block sums, the first-of-table
+  // flags (n), table_first and the index plan (item bases per table, the
+  // items' table and entry, their offsets), the spans and the digests'
+  // descriptors per table; host form: the uploaded arenas and entries, both
+  // images and the digests
+  struct {
+    uint64_t* off = nullptr;
+    size_t cap_off = 0;
+    uint64_t* bsum = nullptr;
+    size_t cap_bsum = 0;
+    uint8_t* first = nullptr;
+    size_t cap_first = 0;
+    uint64_t* tf = nullptr;
+    size_t cap_tf = 0;
+    uint64_t* ibase = nullptr;
+    size_t cap_ibase = 0;
+    uint32_t* item_tab = nullptr;
+    size_t cap_item_tab = 0;
+    uint32_t* item_ent = nullptr;
+    size_t cap_item_ent = 0;
+    uint64_t* ioff = nullptr;
+    size_t cap_ioff = 0;
+    lsmck_sstable_span* spans = nullptr;
+    size_t cap_spans = 0;
+    uint64_t* doff = nullptr;
+    size_t cap_doff = 0;
+    uint32_t* dlen = nullptr;
+    size_t cap_dlen = 0;
+    uint64_t* xoff = nullptr;
+    size_t cap_xoff = 0;
+    uint32_t* xlen = nullptr;
+    size_t cap_xlen = 0;
+    uint8_t* keys = nullptr;
+    size_t cap_keys = 0;
+    uint8_t* vals = nullptr;
+    size_t cap_vals = 0;
+    lsmck_wal_cmd* ents = nullptr;
+    size_t cap_ents = 0;
+    uint8_t* data = nullptr;
+    size_t cap_data = 0;
+    uint8_t* index = nullptr;
+    size_t cap_index = 0;
+    uint8_t* sha = nullptr;  // both digest arrays: 64 bytes per table
+    size_t cap_sha = 0;
+  } sst;  // (its four info words: d_verify[4..7], read back into h_verify[4..7])
+  bool sst_time = false;           // option "sst_encode_time": the encode's stages between device events
+  long sst_ns[4] = {0, 0, 0, 0};   // the last timed encode: scan / order / plan, gather, index writer, digests
+  hipEvent_t sst_ev[6] = {};       // (created by the first timed encode)
   bool wal_recs_direct = false;  // this replay's records go by DMA into the caller's pinned array (under wal_mu)
   bool wal_compact = false;      // this replay's records are lsmck_wal_rec16 (under wal_mu)
   // LSMCK_RECS_DEVICE (under wal_mu): the caller's device array and its capacity
@@ -1286,6 +1335,12 @@ int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value) {
     ctx->enc_time = value != 0;
     return 0;
   }
+  if (!strcmp(key, "sst_encode_time")) {  // diagnostic: lsmck_sstable_encode_batch's stages between device events
+    if (value != 0 && value != 1) return lsmck_host::set_error(LSMCK_EINVAL, "sst_encode_time must be 0 or 1");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->sst_time = value != 0;
+    return 0;
+  }
   return lsmck_host::set_error(LSMCK_EINVAL, "unknown option");
 }
 
@@ -1320,6 +1375,16 @@ int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value) {
     *value = ctx->enc_ns[2];
   } else if (!strcmp(key, "wal_encode_stamp_ns")) {
     *value = ctx->enc_ns[3];
+  } else if (!strcmp(key, "sst_encode_tile")) {  // lsmck_sstable_encode_batch: data bytes per workgroup of the gather
+    *value = (long)lsmk_sst_tile();
+  } else if (!strcmp(key, "sst_encode_scan_ns")) {  // the last timed encode's stages ("sst_encode_time")
+    *value = ctx->sst_ns[0];
+  } else if (!strcmp(key, "sst_encode_gather_ns")) {
+    *value = ctx->sst_ns[1];
+  } else if (!strcmp(key, "sst_encode_index_ns")) {
+    *value = ctx->sst_ns[2];
+  } else if (!strcmp(key, "sst_encode_sha_ns")) {
+    *value = ctx->sst_ns[3];
   } else {
     return lsmck_host::set_error(LSMCK_EINVAL, "unknown stat");
   }
@@ -1359,6 +1424,16 @@ void lsmck_ctx_destroy(lsmck_ctx* ctx) {
                   (void*)ctx->enc.cmds, (void*)ctx->enc.img})
     if (p) (void)hipFree(p);
   for (hipEvent_t e : ctx->enc_ev)
+    if (e) (void)hipEventDestroy(e);
+  {
+    auto& S = ctx->sst;
+    for (void* p : {(void*)S.off, (void*)S.bsum, (void*)S.first, (void*)S.tf, (void*)S.ibase, (void*)S.item_tab,
+                    (void*)S.item_ent, (void*)S.ioff, (void*)S.spans, (void*)S.doff, (void*)S.dlen, (void*)S.xoff,
+                    (void*)S.xlen, (void*)S.keys, (void*)S.vals, (void*)S.ents, (void*)S.data, (void*)S.index,
+                    (void*)S.sha})
+      if (p) (void)hipFree(p);
+  }
+  for (hipEvent_t e : ctx->sst_ev)
     if (e) (void)hipEventDestroy(e);
   if (ctx->h_verify) host_free(ctx->h_verify);
   if (ctx->h_wrecs) host_free(ctx->h_wrecs);
@@ -2607,6 +2682,160 @@ int lsmck_wal_encode_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_byte
       float ms = 0;
       HIPCHK(hipEventElapsedTime(&ms, ev[pair[k][0]], ev[pair[k][1]]));
       ctx->enc_ns[k] = (long)((double)ms * 1e6);
+    }
+  }
+  return 0;
+}
+
+int lsmck_sstable_encode_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes, const uint8_t* vals,
+                               size_t vals_bytes, const lsmck_wal_cmd* ents, size_t n, const uint64_t* table_first,
+                               size_t ntab, uint8_t* data, size_t data_cap, uint8_t* index, size_t index_cap,
+                               lsmck_sstable_span* spans, uint8_t* data_sha, uint8_t* index_sha, size_t* data_bytes,
+                               size_t* index_bytes, uint64_t* bad_index, unsigned flags) {
+  int rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!data_bytes || !index_bytes) return lsmck_host::set_error(LSMCK_EINVAL, "null data_bytes or index_bytes");
+  *data_bytes = *index_bytes = 0;
+  if (bad_index) *bad_index = ~0ull;
+  if (flags & ~(LSMCK_DEVICE | LSMCK_HOST_PINNED))
+    return lsmck_host::set_error(LSMCK_EINVAL, "sstable encode: unknown flag");
+  if (n >= (1ull << 32) || ntab >= (1ull << 32))
+    return lsmck_host::set_error(LSMCK_EINVAL, "sstable encode: more than 2^32-1 entries or tables in one batch");
+  if (n == 0 && ntab == 0) return 0;
+  // table_first, on the host, before any GPU work
+  if (!table_first) return lsmck_host::set_error(LSMCK_EINVAL, "sstable encode: null table_first");
+  if (table_first[0] != 0 || table_first[ntab] != n)
+    return lsmck_host::set_error(LSMCK_EINVAL, "sstable encode: table_first must start at 0 and end at n");
+  for (size_t t = 0; t < ntab; ++t)
+    if (table_first[t + 1] < table_first[t])
+      return lsmck_host::set_error(LSMCK_EINVAL, "sstable encode: table_first decreases");
+  if (n && !ents) return lsmck_host::set_error(LSMCK_EINVAL, "null entries");
+  // the index plan: per table one count item, then an item for every 100th entry
+  std::vector<uint64_t> ibase(ntab + 1);
+  uint64_t nitems = 0;
+  for (size_t t = 0; t < ntab; ++t) {
+    ibase[t] = nitems;
+    nitems += 1 + (table_first[t + 1] - table_first[t] + 99) / 100;
+  }
+  ibase[ntab] = nitems;
+  std::vector<uint32_t> item_tab((size_t)nitems), item_ent((size_t)nitems);
+  for (size_t t = 0; t < ntab; ++t) {
+    size_t k = (size_t)ibase[t];
+    item_tab[k] = (uint32_t)t, item_ent[k++] = 0xFFFFFFFFu;
+    for (uint64_t i = table_first[t]; i < table_first[t + 1]; i += 100) item_tab[k] = (uint32_t)t, item_ent[k++] = (uint32_t)i;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DevGuard g(ctx->dev);
+  const hipStream_t st = ctx->stream0;
+  ScratchOrder so(ctx, st);
+  if (so.e != hipSuccess) return hip_error(so.e, "hipStreamWaitEvent(scratch)");
+  auto& S = ctx->sst;
+  const bool dev = (flags & LSMCK_DEVICE) != 0;
+  const uint8_t *dk = keys, *dv = vals;
+  const lsmck_wal_cmd* dc = ents;
+  if (!dev) {  // staged whole: the arenas (once when they are one buffer) and the entries
+    const bool same = keys == vals && keys_bytes == vals_bytes;
+    if ((rc = ensure_dev(&S.keys, &S.cap_keys, keys_bytes)) || (rc = ensure_dev(&S.ents, &S.cap_ents, n)) ||
+        (!same && (rc = ensure_dev(&S.vals, &S.cap_vals, vals_bytes))))
+      return rc;
+    if (keys_bytes) HIPCHK(hipMemcpyAsync(S.keys, keys, keys_bytes, hipMemcpyHostToDevice, st));
+    if (!same && vals_bytes) HIPCHK(hipMemcpyAsync(S.vals, vals, vals_bytes, hipMemcpyHostToDevice, st));
+    if (n) HIPCHK(hipMemcpyAsync(S.ents, ents, n * sizeof(lsmck_wal_cmd), hipMemcpyHostToDevice, st));
+    dk = S.keys;
+    dv = same ? S.keys : S.vals;
+    dc = S.ents;
+  }
+  const size_t nb = (size_t)std::max(lsmk_sst_scan_blocks(n), lsmk_sst_scan_blocks(nitems)) + 1;
+  if ((rc = ensure_dev(&S.off, &S.cap_off, n + 1)) || (rc = ensure_dev(&S.bsum, &S.cap_bsum, nb)) ||
+      (rc = ensure_dev(&S.first, &S.cap_first, n)) || (rc = ensure_dev(&S.tf, &S.cap_tf, ntab + 1)) ||
+      (rc = ensure_dev(&S.ibase, &S.cap_ibase, ntab + 1)) ||
+      (rc = ensure_dev(&S.item_tab, &S.cap_item_tab, (size_t)nitems)) ||
+      (rc = ensure_dev(&S.item_ent, &S.cap_item_ent, (size_t)nitems)) ||
+      (rc = ensure_dev(&S.ioff, &S.cap_ioff, (size_t)nitems + 1)) || (rc = ensure_dev(&S.spans, &S.cap_spans, ntab)) ||
+      (rc = ensure_dev(&S.doff, &S.cap_doff, ntab)) || (rc = ensure_dev(&S.dlen, &S.cap_dlen, ntab)) ||
+      (rc = ensure_dev(&S.xoff, &S.cap_xoff, ntab)) || (rc = ensure_dev(&S.xlen, &S.cap_xlen, ntab)))
+    return rc;
+  HIPCHK(hipMemcpyAsync(S.tf, table_first, (ntab + 1) * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(S.ibase, ibase.data(), (ntab + 1) * 8, hipMemcpyHostToDevice, st));
+  if (nitems) {
+    HIPCHK(hipMemcpyAsync(S.item_tab, item_tab.data(), (size_t)nitems * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(S.item_ent, item_ent.data(), (size_t)nitems * 4, hipMemcpyHostToDevice, st));
+  }
+  // 1.-3. sizes, validation, offsets; key order; the index items' places; the
+  // spans.  The totals and the two error words come back once.
+  unsigned long long* info = ctx->d_verify + 4;
+  HIPCHK(hipMemsetAsync(info, 0xFF, 32, st));
+  if (n) HIPCHK(hipMemsetAsync(S.first, 0, n, st));
+  const bool timed = ctx->sst_time;
+  hipEvent_t* ev = ctx->sst_ev;
+  if (timed && !ev[0])
+    for (int k = 0; k < 6; ++k) HIPCHK(hipEventCreate(&ev[k]));
+  if (timed) HIPCHK(hipEventRecord(ev[0], st));
+  const unsigned hash = (data_sha ? 1u : 0u) | (index_sha ? 2u : 0u);
+  if ((rc = lsmk_sst_sizes(dc, n, keys_bytes, vals_bytes, S.off, S.bsum, info, st)))
+    return launch_rc(rc, "sstable encode size / scan kernels");
+  if ((rc = lsmk_sst_order(dc, n, dk, keys_bytes, vals_bytes, S.tf, ntab, S.first, info, st)))
+    return launch_rc(rc, "sstable encode order kernels");
+  if ((rc = lsmk_sst_index_plan(S.item_ent, nitems, dc, S.ioff, S.bsum, info, st)))
+    return launch_rc(rc, "sstable encode index plan kernels");
+  if ((rc = lsmk_sst_spans(S.tf, S.ibase, ntab, S.off, S.ioff, S.spans, S.doff, S.dlen, S.xoff, S.xlen, hash, info,
+                           st)))
+    return launch_rc(rc, "sstable encode span kernel");
+  if (timed) HIPCHK(hipEventRecord(ev[1], st));
+  HIPCHK(hipMemcpyAsync(ctx->h_verify + 4, info, 32, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const uint64_t bad = ctx->h_verify[4], total = ctx->h_verify[5], bad_tab = ctx->h_verify[6],
+                 itotal = ctx->h_verify[7];
+  if (bad != ~0ull) {
+    if (bad_index) *bad_index = bad;
+    return lsmck_host::set_error(LSMCK_EINVAL,
+                                 "sstable encode: invalid entry (type, lengths, source range or key order)");
+  }
+  *data_bytes = (size_t)total;
+  *index_bytes = (size_t)itotal;
+  if (bad_tab != ~0ull) {
+    const std::string m = "sstable encode: table " + std::to_string(bad_tab) +
+                          " is above 2^32-1 bytes: its digest cannot be asked for (descriptor lengths are u32)";
+    return lsmck_host::set_error(LSMCK_EINVAL, m.c_str());
+  }
+  if (data_cap < total || index_cap < itotal)
+    return lsmck_host::set_error(LSMCK_ENOSPC, "sstable encode: the data or the index buffer is too small");
+  if ((total && !data) || (itotal && !index)) return lsmck_host::set_error(LSMCK_EINVAL, "null data or index buffer");
+  uint8_t *dd = data, *dx = index, *dsd = data_sha, *dsx = index_sha;
+  if (!dev) {
+    if ((rc = ensure_dev(&S.data, &S.cap_data, (size_t)total)) || (rc = ensure_dev(&S.index, &S.cap_index, (size_t)itotal)) ||
+        (rc = ensure_dev(&S.sha, &S.cap_sha, 64 * ntab)))
+      return rc;
+    dd = S.data, dx = S.index;
+    dsd = data_sha ? S.sha : nullptr;
+    dsx = index_sha ? S.sha + 32 * ntab : nullptr;
+  }
+  // 4. the data gather  5. the index writer  6. the digests
+  if (timed) HIPCHK(hipEventRecord(ev[2], st));
+  if ((rc = lsmk_sst_gather(dk, dv, dc, n, S.off, dd, total, st))) return launch_rc(rc, "sstable encode gather kernel");
+  if (timed) HIPCHK(hipEventRecord(ev[3], st));
+  if ((rc = lsmk_sst_index_write(S.item_tab, S.item_ent, nitems, S.tf, dc, dk, S.off, S.ioff, dx, st)))
+    return launch_rc(rc, "sstable encode index kernel");
+  if (timed) HIPCHK(hipEventRecord(ev[4], st));
+  if (ntab && dsd && (rc = sha_device(ctx, ctx->scratch, dd, S.doff, S.dlen, 0, 0, ntab, dsd, st))) return rc;
+  if (ntab && dsx && (rc = sha_device(ctx, ctx->scratch, dx, S.xoff, S.xlen, 0, 0, ntab, dsx, st))) return rc;
+  if (timed) HIPCHK(hipEventRecord(ev[5], st));
+  if (spans && ntab)
+    HIPCHK(hipMemcpyAsync(spans, S.spans, ntab * sizeof(lsmck_sstable_span),
+                          dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  if (!dev) {
+    if (total) HIPCHK(hipMemcpyAsync(data, dd, (size_t)total, hipMemcpyDeviceToHost, st));
+    if (itotal) HIPCHK(hipMemcpyAsync(index, dx, (size_t)itotal, hipMemcpyDeviceToHost, st));
+    if (dsd) HIPCHK(hipMemcpyAsync(data_sha, dsd, 32 * ntab, hipMemcpyDeviceToHost, st));
+    if (dsx) HIPCHK(hipMemcpyAsync(index_sha, dsx, 32 * ntab, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  if (timed) {
+    const int pair[4][2] = {{0, 1}, {2, 3}, {3, 4}, {4, 5}};
+    for (int k = 0; k < 4; ++k) {
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, ev[pair[k][0]], ev[pair[k][1]]));
+      ctx->sst_ns[k] = (long)((double)ms * 1e6);
     }
   }
   return 0;

@@ -456,6 +456,34 @@ uint64_t lsmck_wal_encoded_size(const lsmck_wal_cmd* cmds, size_t n) {
   return total;
 }
 
+int lsmck_sstable_encoded_size(const lsmck_wal_cmd* ents, size_t n, const uint64_t* table_first, size_t ntab,
+                               uint64_t* data_bytes, uint64_t* index_bytes) {
+  if (data_bytes) *data_bytes = 0;
+  if (index_bytes) *index_bytes = 0;
+  if ((n && !ents) || ((n || ntab) && !table_first))
+    return lsmck_host::set_error(LSMCK_EINVAL, "sstable encoded size: null entries or table_first");
+  if (!ntab && !n) return 0;
+  if (table_first[0] != 0 || table_first[ntab] != n)
+    return lsmck_host::set_error(LSMCK_EINVAL, "sstable encoded size: table_first must start at 0 and end at n");
+  uint64_t data = 0, index = 0;
+  for (size_t t = 0; t < ntab; ++t) {
+    if (table_first[t + 1] < table_first[t] || table_first[t + 1] > n)
+      return lsmck_host::set_error(LSMCK_EINVAL, "sstable encoded size: table_first decreases");
+    index += 8;
+    for (uint64_t i = table_first[t]; i < table_first[t + 1]; ++i) {
+      const lsmck_wal_cmd& c = ents[i];
+      if (c.type != 1) return lsmck_host::set_error(LSMCK_EINVAL, "sstable encoded size: an entry's type is not 1");
+      if (8ull + c.klen + c.vlen > 0xFFFFFFFFull)
+        return lsmck_host::set_error(LSMCK_EINVAL, "sstable encoded size: a record of more than 2^32-1 bytes");
+      data += 8ull + c.klen + c.vlen;
+      if ((i - table_first[t]) % 100 == 0) index += 16ull + c.klen;  // INDEX_STEP (sstable.rs:17)
+    }
+  }
+  if (data_bytes) *data_bytes = data;
+  if (index_bytes) *index_bytes = index;
+  return 0;
+}
+
 void lsmck_gen_zipf_lengths(uint64_t seed, double s, int kmax, uint32_t lmin, size_t n, uint32_t* out) {
   lsmck_host::gen_zipf_lengths(seed, s, kmax, lmin, 0, n, out);
 }

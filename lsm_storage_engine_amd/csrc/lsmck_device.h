@@ -105,6 +105,33 @@ int lsmk_wal_encode_desc(const lsmck_wal_cmd* cmds, uint64_t n, const uint64_t* 
                          hipStream_t st);
 // the records' CRC fields
 int lsmk_wal_encode_stamp(uint8_t* img, const uint64_t* off, const uint32_t* crc, uint64_t n, hipStream_t st);
+// the exclusive scan of nb u64 block sums in place (wal_seg_scan_b alone)
+int lsmk_scan_u64_blocks(uint64_t* bsum, uint32_t nb, hipStream_t st);
+// batch SSTable encode (lsmck_sstable_encode_batch; lsmck_sstable.hip sst_*).
+// info: 4 words the caller sets to ~0 -- [0] the first invalid entry (atomic
+// min), [1] the data arena's bytes, [2] the first table too long to hash
+// (atomic min), [3] the index arena's bytes
+uint32_t lsmk_sst_tile(void);                // the gather's tile bytes
+uint64_t lsmk_sst_scan_blocks(uint64_t n);   // bsum entries of a scan over n values
+// sizes, validation and the exclusive scan: off[0..n]
+int lsmk_sst_sizes(const lsmck_wal_cmd* ents, uint64_t n, uint64_t keys_bytes, uint64_t vals_bytes, uint64_t* off,
+                   uint64_t* bsum, unsigned long long* info, hipStream_t st);
+// key order inside every table (first: n bytes, zeroed by the caller; tf: ntab + 1 on the device)
+int lsmk_sst_order(const lsmck_wal_cmd* ents, uint64_t n, const uint8_t* keys, uint64_t keys_bytes,
+                   uint64_t vals_bytes, const uint64_t* tf, uint64_t ntab, uint8_t* first, unsigned long long* info,
+                   hipStream_t st);
+// the index items' sizes and their scan: ioff[0..nitems]
+int lsmk_sst_index_plan(const uint32_t* item_ent, uint64_t nitems, const lsmck_wal_cmd* ents, uint64_t* ioff,
+                        uint64_t* bsum, unsigned long long* info, hipStream_t st);
+// spans and the digests' descriptors per table; hash: bit 0 the data images are hashed, bit 1 the index images
+int lsmk_sst_spans(const uint64_t* tf, const uint64_t* ibase, uint64_t ntab, const uint64_t* off, const uint64_t* ioff,
+                   lsmck_sstable_span* spans, uint64_t* doff, uint32_t* dlen, uint64_t* xoff, uint32_t* xlen,
+                   unsigned hash, unsigned long long* info, hipStream_t st);
+int lsmk_sst_gather(const uint8_t* keys, const uint8_t* vals, const lsmck_wal_cmd* ents, uint64_t n,
+                    const uint64_t* off, uint8_t* img, uint64_t total, hipStream_t st);
+int lsmk_sst_index_write(const uint32_t* item_tab, const uint32_t* item_ent, uint64_t nitems, const uint64_t* tf,
+                         const lsmck_wal_cmd* ents, const uint8_t* keys, const uint64_t* off, const uint64_t* ioff,
+                         uint8_t* index, hipStream_t st);
 int lsmk_wal_emit(const uint8_t* img, uint64_t n, const uint32_t* chain, const uint64_t* pos,
                   const unsigned long long* info, uint32_t m, lsmck_wal_rec* recs, uint64_t* poff, uint32_t* plen,
                   uint32_t* pcrc, hipStream_t st);

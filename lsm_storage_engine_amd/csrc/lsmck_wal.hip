@@ -852,6 +852,12 @@ extern "C" int lsmk_wal_encode_scan(const lsmck_wal_cmd* cmds, uint64_t n, uint6
                      (const uint64_t*)bsum, off, info);
   return launch_err();
 }
+// pass b of a three-pass u64 scan alone (wal_seg_scan_b: the exclusive scan of
+// nb block sums in place), for the scans of other files (lsmck_sstable.hip)
+extern "C" int lsmk_scan_u64_blocks(uint64_t* bsum, uint32_t nb, hipStream_t st) {
+  hipLaunchKernelGGL(wal_seg_scan_b, dim3(1), dim3(1024), 0, st, bsum, nb);
+  return launch_err();
+}
 extern "C" int lsmk_wal_encode_gather(const uint8_t* keys, const uint8_t* vals, const lsmck_wal_cmd* cmds, uint64_t n,
                                       const uint64_t* off, uint8_t* img, uint64_t total, hipStream_t st) {
   if (n == 0 || total == 0) return 0;

@@ -103,6 +103,18 @@ class WalEncodeError(_lib.LsmckError):
         super().__init__(rc, f"{what} (bad_index={bad_index}, needed={needed})")
 
 
+class SstEncodeError(_lib.LsmckError):
+    """lsmck_sstable_encode_batch refused the batch: ``bad_index`` is the first
+    offending entry (LSMCK_EINVAL; None when the error is table_first's or a
+    table too long to hash), or ``needed`` = (data bytes, index bytes) when a
+    buffer given is smaller (LSMCK_ENOSPC); the other one is None."""
+
+    def __init__(self, rc, what, bad_index=None, needed=None):
+        self.bad_index = bad_index
+        self.needed = needed
+        super().__init__(rc, f"{what} (bad_index={bad_index}, needed={needed})")
+
+
 class Context:
     def __init__(self, device=0):
         lib = _lib.load()
@@ -315,6 +327,63 @@ class Context:
         (cap is smaller than the encoded size); nothing was written then."""
         return self._wal_encode(keys_ptr, keys_bytes, vals_ptr, vals_bytes, cmds_ptr, n, img_ptr, cap, rec_off_ptr,
                                 _lib.DEVICE)
+
+    def _sst_encode(self, keys, kb, vals, vb, ents, n, table_first, data, data_cap, index, index_cap, spans,
+                    data_sha, index_sha, flags):
+        none = 2 ** 64 - 1
+        tf = np.ascontiguousarray(table_first, dtype=np.uint64)
+        if len(tf) < 1:
+            raise ValueError("table_first holds ntab + 1 values")
+        db, ib, bad = C.c_size_t(), C.c_size_t(), C.c_uint64(none)
+        rc = self.lib.lsmck_sstable_encode_batch(self.handle, keys, kb, vals, vb, ents, n, tf.ctypes.data, len(tf) - 1,
+                                                 data, data_cap, index, index_cap, spans, data_sha, index_sha,
+                                                 C.byref(db), C.byref(ib), C.byref(bad), flags)
+        if rc == _lib.EINVAL:
+            raise SstEncodeError(rc, "sstable_encode_batch", bad_index=None if bad.value == none else bad.value)
+        if rc == _lib.ENOSPC:
+            raise SstEncodeError(rc, "sstable_encode_batch", needed=(db.value, ib.value))
+        _lib.check(rc, "sstable_encode_batch")
+        return db.value, ib.value
+
+    def sstable_encode_batch(self, keys, vals, ents, table_first, digests=True, pinned=False):
+        """lsmck_sstable_encode_batch, host form: the data and index files of
+        the tables that ``table_first`` (ntab + 1 entry indices) cuts the
+        entries ``ents`` (WAL_CMD_DTYPE, type 1: key / value ranges in the
+        uint8 arenas ``keys`` / ``vals``, which may be one array) into,
+        encoded and hashed on the GPU.  Returns (data, index: np.uint8 arrays,
+        the tables' files back to back; spans: SSTABLE_SPAN_DTYPE per table;
+        data_sha, index_sha: (ntab, 32) uint8, or None without ``digests``).
+        Raises SstEncodeError (``bad_index``: the first offending entry)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint8)
+        vals = keys if vals is keys else np.ascontiguousarray(vals, dtype=np.uint8)
+        ents = np.ascontiguousarray(ents, dtype=_lib.WAL_CMD_DTYPE)
+        tf = np.ascontiguousarray(table_first, dtype=np.uint64)
+        n, ntab = len(ents), len(tf) - 1
+        db, ib = C.c_uint64(), C.c_uint64()
+        if self.lib.lsmck_sstable_encoded_size(ents.ctypes.data, n, tf.ctypes.data, ntab, C.byref(db), C.byref(ib)):
+            db, ib = C.c_uint64(0), C.c_uint64(0)  # (the call reports what is wrong)
+        data, index = np.empty(db.value, dtype=np.uint8), np.empty(ib.value, dtype=np.uint8)
+        spans = np.empty(ntab, dtype=_lib.SSTABLE_SPAN_DTYPE)
+        dsha = np.empty((ntab, 32), dtype=np.uint8) if digests else None
+        isha = np.empty((ntab, 32), dtype=np.uint8) if digests else None
+        flags = _lib.HOST_PINNED if pinned else _lib.HOST
+        got = self._sst_encode(keys.ctypes.data, keys.nbytes, vals.ctypes.data, vals.nbytes, ents.ctypes.data, n, tf,
+                               data.ctypes.data, data.nbytes, index.ctypes.data, index.nbytes, spans.ctypes.data,
+                               _p(dsha), _p(isha), flags)
+        assert got == (db.value, ib.value)
+        return data, index, spans, dsha, isha
+
+    def sstable_encode_batch_device(self, keys_ptr, keys_bytes, vals_ptr, vals_bytes, ents_ptr, n, table_first,
+                                    data_ptr, data_cap, index_ptr, index_cap, spans_ptr=None, data_sha_ptr=None,
+                                    index_sha_ptr=None):
+        """lsmck_sstable_encode_batch on device pointers (ents: n lsmck_wal_cmd;
+        table_first: a host array of ntab + 1 values; spans_ptr: ntab
+        lsmck_sstable_span or None; the digest pointers: 32 * ntab bytes each
+        or None -- that image is not hashed).  Returns (data_bytes,
+        index_bytes); raises SstEncodeError with ``bad_index`` or ``needed``;
+        nothing was written then."""
+        return self._sst_encode(keys_ptr, keys_bytes, vals_ptr, vals_bytes, ents_ptr, n, table_first, data_ptr,
+                                data_cap, index_ptr, index_cap, spans_ptr, data_sha_ptr, index_sha_ptr, _lib.DEVICE)
 
     def wal_replay_verify(self, image, device_ptr=None, cap=None, pinned_recs=False, compact=False):
         """Returns (records, status, (bad_index, bad_crc, bad_expected)).

@@ -1,0 +1,140 @@
+"""Writing SSTables -- the host-side mirror of ``SsTable::from_memtable``
+(src/tokio/sstable.rs:84-129, src/sync/sstable.rs:135-141,241-253).
+
+A table is five files named by ``SsTableMetadata``: the data file
+(``[u32 klen][u32 vlen][key][val]`` per entry in key order, datafile.rs:27-35),
+the index file (bincode of the BTreeMap that maps every INDEX_STEP-th key to
+its record's position, sstable_index.rs:42-46), the checksum JSON
+(checksums.rs:64-80: ``index_checksum`` first, the file opened without
+truncate), an empty bloom filter file (bloom filters are out of scope here, as
+for ``tree.synthesize_tree``) and the metadata JSON.
+
+``from_memtable`` writes one table; ``flush_many`` writes many from one GPU
+call (``lsmck_sstable_encode_batch``: the data and index images of every table
+and their SHA-256 digests).  Without a context the bytes are built here and
+hashed by the scalar path (``Checksums.write_checksums``); the files are the
+same either way.
+"""
+import ctypes as C
+import os
+import struct
+import time
+
+import numpy as np
+
+from . import _lib
+from .checksums import Checksums
+from .sstable_metadata import SsTableMetadata
+
+INDEX_STEP = 100  # src/tokio/sstable.rs:17
+
+
+def _entries(memtable):
+    """(key, value) pairs in the memtable's BTreeMap order: a wal.MemTable, a
+    dict, or an iterable of pairs."""
+    items = memtable.data.items() if hasattr(memtable, "data") else \
+        memtable.items() if hasattr(memtable, "items") else memtable
+    return sorted((bytes(k), bytes(v)) for k, v in items)
+
+
+def table_bytes(entries):
+    """One table's data and index file contents from its sorted entries."""
+    data, index, pos = bytearray(), [], 0
+    for i, (k, v) in enumerate(entries):
+        if i % INDEX_STEP == 0:
+            index.append((k, pos))
+        data += struct.pack("<II", len(k), len(v)) + k + v
+        pos += 8 + len(k) + len(v)
+    idx = bytearray(struct.pack("<Q", len(index)))
+    for k, p in index:
+        idx += struct.pack("<Q", len(k)) + k + struct.pack("<Q", p)
+    return bytes(data), bytes(idx)
+
+
+def batch_arrays(tables):
+    """The arenas, entries (WAL_CMD_DTYPE, type 1) and table_first of
+    lsmck_sstable_encode_batch for a list of tables' sorted entries: keys back
+    to back in one arena, values in another."""
+    flat = [e for t in tables for e in t]
+    n = len(flat)
+    ents = np.zeros(n, dtype=_lib.WAL_CMD_DTYPE)
+    klen = np.fromiter((len(k) for k, _ in flat), dtype=np.uint64, count=n)
+    vlen = np.fromiter((len(v) for _, v in flat), dtype=np.uint64, count=n)
+    ents["klen"], ents["vlen"], ents["type"] = klen, vlen, 1
+    ents["key_off"], ents["val_off"] = np.cumsum(klen) - klen, np.cumsum(vlen) - vlen
+    keys = np.frombuffer(b"".join(k for k, _ in flat), dtype=np.uint8)
+    vals = np.frombuffer(b"".join(v for _, v in flat), dtype=np.uint8)
+    first = np.zeros(len(tables) + 1, dtype=np.uint64)
+    first[1:] = np.cumsum([len(t) for t in tables])
+    return keys, vals, ents, first
+
+
+def _b64(digest):
+    raw = bytes(digest)
+    out = C.create_string_buffer(45)
+    _lib.load().lsmck_base64_encode(raw, len(raw), out)
+    return out.value.decode()
+
+
+def _write_no_truncate(path, payload):
+    fd = os.open(path, os.O_WRONLY | os.O_CREAT, 0o644)  # .write(true).create(true): no truncate, as the reference
+    try:
+        os.write(fd, payload)
+    finally:
+        os.close(fd)
+
+
+def _write_checksum_json(path, index_sha, data_sha):
+    """checksums.rs:64-80 from digests already computed: serde_json's compact
+    form, index_checksum first, what lsmck_checksums_write leaves."""
+    s = '{"index_checksum":"%s","data_checksum":"%s"}' % (_b64(index_sha), _b64(data_sha))
+    _write_no_truncate(path, s.encode())
+
+
+def _write_table(m, data, index, index_sha=None, data_sha=None):
+    os.makedirs(os.path.dirname(m.data_path()), exist_ok=True)
+    with open(m.data_path(), "wb") as f:
+        f.write(data)
+    with open(m.index_path(), "wb") as f:
+        f.write(index)
+    if index_sha is None:
+        Checksums.write_checksums(m)  # the scalar path: both files read back and hashed on this thread
+    else:
+        _write_checksum_json(m.checksum_path(), index_sha, data_sha)
+    open(m.bloom_filter_path(), "wb").close()
+    m.write_to_file()
+    return m
+
+
+def flush_many(base_path, level, memtables, ctx, timestamps_ms=None):
+    """Write one table per memtable under ``<base_path>/level-<level>``.  With
+    a context every table's data and index image and both digests come from
+    one lsmck_sstable_encode_batch call; with ``ctx=None`` they are built here
+    and hashed one file at a time.  Returns the tables' SsTableMetadata."""
+    tables = [_entries(mt) for mt in memtables]
+    if timestamps_ms is None:
+        t0 = int(time.time() * 1000)
+        timestamps_ms = [t0 + i for i in range(len(tables))]
+    metas = [SsTableMetadata.new(str(base_path), level, timestamp_ms=ts) for ts in timestamps_ms]
+    assert len(metas) == len(tables)
+    if ctx is None:
+        return [_write_table(m, *table_bytes(t)) for m, t in zip(metas, tables)]
+    if not tables:
+        return []
+    keys, vals, ents, first = batch_arrays(tables)
+    data, index, spans, dsha, isha = ctx.sstable_encode_batch(keys, vals, ents, first)
+    for t, m in enumerate(metas):
+        s = spans[t]
+        d0, i0 = int(s["data_off"]), int(s["index_off"])
+        _write_table(m, memoryview(data)[d0:d0 + int(s["data_len"])], memoryview(index)[i0:i0 + int(s["index_len"])],
+                     isha[t], dsha[t])
+    return metas
+
+
+def from_memtable(base_path, memtable, ctx=None, timestamp_ms=None):
+    """SsTable::from_memtable: the memtable as a level-0 table.  Returns its SsTableMetadata."""
+    ts = None if timestamp_ms is None else [timestamp_ms]
+    return flush_many(base_path, 0, [memtable], ctx, ts)[0]
+
+
+__all__ = ["from_memtable", "flush_many", "table_bytes", "batch_arrays", "INDEX_STEP"]
