@@ -690,7 +690,7 @@ int crc_desc_device(lsmck_ctx* ctx, DescScratch& sc, const uint8_t* base, const 
     // walking kernel below takes it, else that kernel exits at once)
     if (!sc.sflag) HIPCHK(hipMalloc((void**)&sc.sflag, 16));
     const int g = ncu > 0 && ncu < ctx->ncu ? ncu : ctx->ncu;
-    if ((rc = ensure_dev(&sc.scuts, &sc.cap_cuts, (size_t)lsmk_stream_waves(ctx->ncu) + 1))) return rc;
+    if ((rc = ensure_dev(&sc.scuts, &sc.cap_cuts, (size_t)lsmk_stream_slices_max(ctx->ncu) + 1))) return rc;
     P.sflag = sc.sflag;
     P.scuts = sc.scuts;
     rc = lsmk_launch_crc32_stream(&P, g, ctx->variant, trusted ? 1 : 0, st);

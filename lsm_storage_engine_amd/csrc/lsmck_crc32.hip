@@ -34,6 +34,12 @@
 //     are built once per CU), 16 waves per CU, each wave walks 64-segment tiles.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#ifdef LSMCK_WAVE_DIAG
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <vector>
+#endif
 
 #include "lsmck_device.h"
 
@@ -144,6 +150,24 @@ __device__ __forceinline__ uint32_t crc_step_x(const unsigned char* smem, uint32
   const uint32_t l2 = lds_ld(smem, a2 + 128u), l3 = lds_ld(smem, a3);
   const uint32_t t = __builtin_amdgcn_bitop3_b32(l2, l3, w_next, 0x96);
   return __builtin_amdgcn_bitop3_b32(lds_ld(smem, a0 + 128u), lds_ld(smem, a1), t, 0x96);
+}
+
+// The step on two chains at once, all eight lookups issued before the first
+// XOR.  The stream kernel's event loop uses it: with its word bodies as
+// branches the two crc_step_x calls came out one after the other, each
+// waiting for its own lookups (two LDS round trips per word and chain).
+__device__ __forceinline__ void crc_step_x2(uint32_t& c0, uint32_t& c1, uint32_t x0, uint32_t n0, uint32_t x1,
+                                            uint32_t n1, uint32_t lo, uint32_t hi) {
+  const uint32_t a00 = __builtin_amdgcn_perm(x0, hi, 0x0c020400u), a01 = __builtin_amdgcn_perm(x0, hi, 0x0c020500u);
+  const uint32_t a02 = __builtin_amdgcn_perm(x0, lo, 0x0c0c0600u), a03 = __builtin_amdgcn_perm(x0, lo, 0x0c0c0700u);
+  const uint32_t a10 = __builtin_amdgcn_perm(x1, hi, 0x0c020400u), a11 = __builtin_amdgcn_perm(x1, hi, 0x0c020500u);
+  const uint32_t a12 = __builtin_amdgcn_perm(x1, lo, 0x0c0c0600u), a13 = __builtin_amdgcn_perm(x1, lo, 0x0c0c0700u);
+  const uint32_t l02 = lds_ld(nullptr, a02 + 128u), l03 = lds_ld(nullptr, a03);
+  const uint32_t l00 = lds_ld(nullptr, a00 + 128u), l01 = lds_ld(nullptr, a01);
+  const uint32_t l12 = lds_ld(nullptr, a12 + 128u), l13 = lds_ld(nullptr, a13);
+  const uint32_t l10 = lds_ld(nullptr, a10 + 128u), l11 = lds_ld(nullptr, a11);
+  c0 = __builtin_amdgcn_bitop3_b32(l00, l01, __builtin_amdgcn_bitop3_b32(l02, l03, n0, 0x96), 0x96);
+  c1 = __builtin_amdgcn_bitop3_b32(l10, l11, __builtin_amdgcn_bitop3_b32(l12, l13, n1, 0x96), 0x96);
 }
 
 // ---------------------------------------------------------------------------
@@ -1007,8 +1031,9 @@ __global__ __launch_bounds__(1024) void crc32_walk_kernel(CrcParams P) {
 // The window: records bt + lane (off, len), loaded one tile ahead and slid by
 // the count of records that end in the tile (ds_bpermute; only the new
 // entries are loaded).  A tile in which all 64 window records end walks the
-// next 64 too.  Each wave owns the records [scuts[w], scuts[w+1]) (stream_cuts:
-// balanced by bytes) and the tiles that hold them; the first tile of a wave
+// next 64 too.  Slice s holds the records [scuts[s], scuts[s+1]) (stream_cuts:
+// balanced by bytes) and the tiles that hold them; a wave takes slice after
+// slice (one per wave on a small batch).  The first tile of a slice
 // starts at its first record's start (the bytes in front are dropped).
 // Eligibility: every batch the library builds itself (host-staged chunks, WAL
 // replay) is sorted by construction and its gaps lie inside one buffer; a
@@ -1131,7 +1156,7 @@ __device__ __forceinline__ uint32_t stream_capture(const unsigned char* smem, ui
 // A caller's batch: the eligibility check, four records per thread (off[]
 // as two 16-byte loads and len[] as one when both arrays are 16-byte aligned,
 // element loads otherwise); the next thread's first record comes from the
-// next lane (lane 63 loads it).  The per-wave cuts follow by binary search
+// next lane (lane 63 loads it).  The slices' cuts follow by binary search
 // (stream_cuts, sorted by then).  One record per thread ran 0.18 ms on config
 // 3; a fused check + cuts pass 0.31 ms.
 // cut w, w = 0..W: the first record starting at or after off[0] + span*w/W
@@ -1160,6 +1185,7 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void stream_check(CrcParams P, uint32_t W) {
   const uint64_t n = P.nrec;
   const uint32_t gt = blockIdx.x * 256u + threadIdx.x;
+  if (gt == 0u) P.sflag[1] = 0u;  // the stream kernel's slice tickets
   if (gt <= W) stream_cut(P, gt, W);
   const uint64_t i0 = (uint64_t)gt * 4u;  // (threads past the records load record n-1 and find nothing)
   uint64_t o[5];
@@ -1199,6 +1225,7 @@ __global__ __launch_bounds__(256) void stream_check(CrcParams P, uint32_t W) {
 // the cuts alone (trusted batches: no check)
 __global__ __launch_bounds__(256) void stream_cuts(CrcParams P, uint32_t W) {
   const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w == 0u) P.sflag[1] = 0u;  // the stream kernel's slice tickets
   if (w > W || !*P.sflag) return;
   stream_cut(P, w, W);
 }
@@ -1287,9 +1314,32 @@ __device__ __forceinline__ uint32_t horner(uint32_t v, uint32_t d) {
 // per active lane, and its tables put the kernel at 8 spilled SGPRs.)
 __device__ __forceinline__ uint32_t finish_mul(uint32_t v, uint32_t m) { return stream_mulcol(v, LDS_XMC_OFF(m)); }
 
+#ifdef LSMCK_WAVE_DIAG
+// Diagnostic builds only (EXTRA=-DLSMCK_WAVE_DIAG tools/build_ab.sh <name> WT;
+// tools/wave_tail.py reads the dump): per wave, the constant 100 MHz clock at
+// the kernel's entry and exit, its tile counts (event tiles << 32 | tiles
+// without events) and where it ran (HW_ID | XCC_ID << 32).
+#define LSMCK_WAVE_DIAG_MAX 8192u
+__device__ uint64_t g_wave_diag[LSMCK_WAVE_DIAG_MAX][4];
+#define WAVE_DIAG(...) __VA_ARGS__
+#else
+#define WAVE_DIAG(...)
+#endif
+
 template <int ABLATE = 0>
 __global__ __launch_bounds__(1024) void crc32_stream_kernel(CrcParams P) {
   if (!*P.sflag) return;  // a caller's batch that is not sorted / packed enough: the walking kernel takes it
+  WAVE_DIAG(const uint64_t diag_t0 = wall_clock64(); uint32_t diag_ev = 0; uint32_t diag_no = 0;)
+  WAVE_DIAG(auto diag_out = [&] {
+    const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if ((threadIdx.x & 63u) == 0u && w < LSMCK_WAVE_DIAG_MAX) {
+      g_wave_diag[w][0] = diag_t0;
+      g_wave_diag[w][1] = wall_clock64();
+      g_wave_diag[w][2] = ((uint64_t)diag_ev << 32) | diag_no;
+      g_wave_diag[w][3] = (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
+                          ((uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
+    }
+  };)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   build_lds_tables(smem, P);
   __syncthreads();  // the Horner tables reuse the cols + khi areas, the finish's x^(8m) the shift-by-32/96 tables' areas
@@ -1317,12 +1367,35 @@ __global__ __launch_bounds__(1024) void crc32_stream_kernel(CrcParams P) {
   const uint32_t lo = (lane & 31u) * 4u, hi = lo | 0x10000u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
   const uint64_t n = P.nrec;
-  const uint64_t r_lo = P.scuts[wave], r_hi = P.scuts[wave + 1];
-  if (r_lo >= r_hi) return;  // no record in this wave's range
   const uint64_t dend = P.off[n - 1] + P.len[n - 1];
   const uintptr_t end4 = ((uintptr_t)P.base + dend + 3u) & ~(uintptr_t)3;
   // chunk grid origin, relative to P.base (128-byte aligned in memory)
   const int64_t a0 = (int64_t)((((uintptr_t)P.base + P.off[0]) & ~(uintptr_t)127) - (uintptr_t)P.base);
+  // The batch is cut into P.nslice slices of equal bytes (stream_cut), several
+  // per wave on a large batch.  A wave takes slice `wave` first and then the
+  // next slice nobody has taken (a ticket counter behind the flag), until none
+  // is left: the waves of a CU finish a launch up to 3 ms apart when each owns
+  // one fixed share (tools/wave_tail.py), with the same tile counts -- the
+  // SIMD's issue arbitration, not the work, decides -- and a wave that is done
+  // early now goes on with work the late ones would have been left with.
+  // (what a slice's start and end need of the launch is read from the kernel
+  // arguments again, through a pointer the compiler cannot see through: held
+  // in SGPRs across the tiles, these values were spilled)
+  typedef __attribute__((address_space(4))) const CrcParams kargs_t;
+  kargs_t* ka = (kargs_t*)__builtin_amdgcn_kernarg_segment_ptr();
+  for (uint32_t slice = wave;;) {
+  asm volatile("" : "+s"(ka));
+  const uint32_t nslice = ka->nslice, nwaves = ka->nwaves;
+  if (slice >= nslice) break;
+  const uint64_t r_lo = ka->scuts[slice], r_hi = ka->scuts[slice + 1];
+  if (nslice > nwaves) {  // the next slice's ticket (a batch of one slice per wave takes none)
+    uint32_t tk = 0;
+    if (lane == 0u) tk = atomicAdd(ka->sflag + 1, 1u);
+    slice = nwaves + (uint32_t)__builtin_amdgcn_readfirstlane((int)tk);
+  } else {
+    slice = nslice;
+  }
+  if (r_lo >= r_hi) continue;  // no record in this slice
   const uint64_t t_first = (uint64_t)((int64_t)P.off[r_lo] - a0) >> 13;
   const uint64_t t_last = (uint64_t)((int64_t)(P.off[r_hi - 1] + P.len[r_hi - 1]) - a0) >> 13;
   // (a batch that is not sorted never gets here; the clamp keeps the loop
@@ -1343,7 +1416,7 @@ __global__ __launch_bounds__(1024) void crc32_stream_kernel(CrcParams P) {
   uint32_t carry = 0;  // the record open at the tile's end, its raw value aligned to the tile's end
   win_load(bt);
   // The CRCs are queued in one VGPR (lane p: record qb + p, qb a multiple of
-  // 64) and stored as whole 256-byte blocks: a wave's records are
+  // 64) and stored as whole 256-byte blocks: a slice's records are
   // consecutive, so only its first and last blocks are partial.  Per-tile
   // stores of the ~5 records a tile ends wrote partial 128-byte lines (the
   // config-3 PMC counted 5.9 GB of fetches for the 0.27 GB output,
@@ -1351,9 +1424,9 @@ __global__ __launch_bounds__(1024) void crc32_stream_kernel(CrcParams P) {
   uint32_t qv = 0;
   uint64_t qb = r_lo & ~63ull;
   uint32_t qs = (uint32_t)(r_lo & 63u), qf = qs;  // first valid lane of the block, next lane to fill
-  auto qstore = [&](uint32_t v, bool on) {  // block qb from a uniform base: no 64-bit lane address to keep
+  auto qstore = [&](uint32_t v, bool on, uint32_t* out) {  // block qb from a uniform base: no 64-bit lane address to keep
     const __amdgpu_buffer_rsrc_t r =
-        __builtin_amdgcn_make_buffer_rsrc((void*)(P.out + qb), (short)0, 256, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc((void*)(out + qb), (short)0, 256, 0x00020000);
     // (ABLATE 6, diagnostic: no output stores -- unless a magic value keeps the checksums alive)
     if (on && (ABLATE != 6 || v == 0x9E3779B1u)) __builtin_amdgcn_raw_buffer_store_b32(v, r, lane << 2, 0, 0);
   };
@@ -1363,7 +1436,7 @@ __global__ __launch_bounds__(1024) void crc32_stream_kernel(CrcParams P) {
     const uint32_t end = qf + cnt;  // at most one block completes
     qv = (lane >= qf && lane < end) ? val : qv;
     if (end >= 64u) {
-      qstore(qv, lane >= qs);
+      qstore(qv, lane >= qs, P.out);
       qb += 64u;
       qs = 0u;
       qf = end - 64u;
@@ -1489,6 +1562,7 @@ __global__ __launch_bounds__(1024) void crc32_stream_kernel(CrcParams P) {
       // (ABLATE 4 / 5, diagnostic: every tile takes this path -- the bulk
       // chains + Horner cost without / with the payload loads)
       if (z || ABLATE == 4 || ABLATE == 5 || ABLATE == 12) {  // (uniform) no event in the tile
+        WAVE_DIAG(++diag_no;)
         bulk(U);
         return;
       }
@@ -1500,6 +1574,7 @@ __global__ __launch_bounds__(1024) void crc32_stream_kernel(CrcParams P) {
     // 19.61-19.68 -> 19.21-19.32 (profiles/r06/prio; priority 2 over the word
     // loop alone 18.90 / 19.23).
     __builtin_amdgcn_s_setprio(1);
+    WAVE_DIAG(++diag_ev;)
     // --- chunk-lane view: this chunk's events (byte + 1 in its chain, 0 = none)
     typedef __attribute__((address_space(3))) uint32_t lds_u32w_t;
     uint32_t ev = *(lds_u32w_t*)(size_t)(smap + 4u * lane);
@@ -1530,31 +1605,48 @@ __global__ __launch_bounds__(1024) void crc32_stream_kernel(CrcParams P) {
       uint32_t i0 = c0, i1 = c1, n0 = w0, n1 = w1;
       // each chain's body only where some lane has an event in that chain's
       // word k (uniform), not wherever either chain has one
+      // The body's assignments run under the EXEC mask, on the lanes that hold
+      // the event (one or two of the 64), as plain moves: as selects on SGPR
+      // masks (v_cndmask_b32_e64, half rate: tools/microbench_valu.hip) every
+      // lane paid four of them per chain and word.  The empty asm on the
+      // assigned values keeps the blocks from being if-converted back.
+      // All four fields of ev are decoded by one add: b + 3 <= 67 carries into
+      // no neighbour, and chain byte j = b - 1 lies in word k  <=>
+      // (b + 3) >> 2 == k + 1 (b = 0, no event, gives 0); a packed boundary's
+      // end and start (equal fields) share that decode.
       if (Km & (1u << k)) {
         uint32_t e = ev;
         asm volatile("" : "+v"(e));  // recomputed here, not hoisted: fewer VGPRs through the loop
-        const uint32_t be0 = e & 0xFFu, bs0 = (e >> 8) & 0xFFu;
-        // chain byte j + 1 at word k: (j >> 2) == k  <=>  ((b - 1) >> 2) == k, b != 0
-        const bool me0 = be0 && ((be0 - 1u) >> 2) == (uint32_t)k, ms0 = bs0 && ((bs0 - 1u) >> 2) == (uint32_t)k;
-        const uint32_t mlo0 = (1u << (((bs0 - 1u) & 3u) << 3)) - 1u;
-        x0 = me0 ? c0 : x0;
-        ub0 = me0 ? U[k] : ub0;
-        i0 = ms0 ? ~(U[k] | mlo0) : c0;
-        n0 = ms0 ? (w0 ^ mlo0) : w0;
+        const uint32_t e3 = e + 0x03030303u;
+        if (((e3 >> 2) & 0x3Fu) == (uint32_t)(k + 1)) {
+          x0 = c0;
+          ub0 = U[k];
+          asm volatile("" : "+v"(x0), "+v"(ub0));
+        }
+        if (((e3 >> 10) & 0x3Fu) == (uint32_t)(k + 1)) {
+          const uint32_t mlo0 = (1u << ((e3 >> 5) & 0x18u)) - 1u;  // the word's bytes in front of the start
+          i0 = ~(U[k] | mlo0);
+          n0 = w0 ^ mlo0;
+          asm volatile("" : "+v"(i0), "+v"(n0));
+        }
       }
       if (Km & (1u << (16 + k))) {
         uint32_t e = ev;
         asm volatile("" : "+v"(e));
-        const uint32_t be1 = (e >> 16) & 0xFFu, bs1 = e >> 24;
-        const bool me1 = be1 && ((be1 - 1u) >> 2) == (uint32_t)k, ms1 = bs1 && ((bs1 - 1u) >> 2) == (uint32_t)k;
-        const uint32_t mlo1 = (1u << (((bs1 - 1u) & 3u) << 3)) - 1u;
-        x1 = me1 ? c1 : x1;
-        ub1 = me1 ? U[16 + k] : ub1;
-        i1 = ms1 ? ~(U[16 + k] | mlo1) : c1;
-        n1 = ms1 ? (w1 ^ mlo1) : w1;
+        const uint32_t e3 = e + 0x03030303u;
+        if (((e3 >> 18) & 0x3Fu) == (uint32_t)(k + 1)) {
+          x1 = c1;
+          ub1 = U[16 + k];
+          asm volatile("" : "+v"(x1), "+v"(ub1));
+        }
+        if ((e3 >> 26) == (uint32_t)(k + 1)) {
+          const uint32_t mlo1 = (1u << ((e3 >> 21) & 0x18u)) - 1u;
+          i1 = ~(U[16 + k] | mlo1);
+          n1 = w1 ^ mlo1;
+          asm volatile("" : "+v"(i1), "+v"(n1));
+        }
       }
-      c0 = crc_step_x(smem, i0, n0, lo, hi);
-      c1 = crc_step_x(smem, i1, n1, lo, hi);
+      crc_step_x2(c0, c1, i0, n0, i1, n1, lo, hi);
     }
     const uint32_t cap0 = ke0 ? stream_capture(smem, x0, ub0, ((ev & 0xFFu) - 1u) & 3u, lo) : 0u;
     const uint32_t cap1 = ke1 ? stream_capture(smem, x1, ub1, (((ev >> 16) & 0xFFu) - 1u) & 3u, lo) : 0u;
@@ -1636,8 +1728,11 @@ __global__ __launch_bounds__(1024) void crc32_stream_kernel(CrcParams P) {
   }
   if (i < ntile) process(U0, t_first + i, none);
   if ((ABLATE == 4 || ABLATE == 5 || ABLATE == 7 || ABLATE >= 9) && carry == 0x9E3779B1u) P.out[0] = carry;  // keeps the ablated chains (and loads) alive
-  if (ABLATE == 3) return;
-  qstore(qv, lane >= qs && lane < qf);
+  if (ABLATE == 3) continue;
+  asm volatile("" : "+s"(ka));  // (as above: P.out, kept for this one store, was spilled)
+  qstore(qv, lane >= qs && lane < qf, ka->out);
+  }  // (the wave's next slice)
+  WAVE_DIAG(diag_out();)
 }
 }  // namespace lsmck
 
@@ -1684,7 +1779,19 @@ extern "C" int lsmk_launch_crc32_fixed(const CrcParams* P, int ncu, int variant,
   return launch_fixed<false, false>(P, ncu, st);
 }
 
-extern "C" uint32_t lsmk_stream_waves(int ncu) { return (uint32_t)ncu * 16u; }
+// Slices of a stream batch: one per wave (16 waves per CU), and on a batch of
+// at least 64 records per slice STREAM_SLICES per wave, which the waves take
+// one after the other (crc32_stream_kernel).  A slice costs its wave a
+// restart -- the window, a first tile that is not prefetched, the tile at the
+// cut read by both neighbours -- so it is kept at tens of tiles or more.
+#ifndef STREAM_SLICES
+#define STREAM_SLICES 16u
+#endif
+extern "C" uint32_t lsmk_stream_slices_max(int ncu) { return (uint32_t)ncu * 16u * STREAM_SLICES; }
+static uint32_t stream_slices(int ncu, uint64_t n) {
+  const uint64_t w = (uint64_t)ncu * 16u;
+  return (uint32_t)std::min<uint64_t>(w * STREAM_SLICES, std::max<uint64_t>(w, n / 64u));
+}
 
 // whether this library carries the stream kernel's diagnostic ablations (crc_ablate 2, 4..10)
 extern "C" int lsmk_ab_ablations() {
@@ -1696,7 +1803,7 @@ extern "C" int lsmk_ab_ablations() {
 }
 
 // stream kernel: eligibility flag (trusted: the library's own batch, sorted
-// with its gaps inside one buffer, so no check), per-wave cuts, the kernel.
+// with its gaps inside one buffer, so no check), the slices' cuts, the kernel.
 // The walking kernel launched after it on the same stream exits when the flag
 // is set.
 extern "C" int lsmk_launch_crc32_stream(const CrcParams* P, int ncu, int variant, int trusted, hipStream_t st) {
@@ -1704,7 +1811,7 @@ extern "C" int lsmk_launch_crc32_stream(const CrcParams* P, int ncu, int variant
   if (n == 0) return 0;
   hipError_t e = hipMemsetAsync(P->sflag, 1, 4, st);
   if (e != hipSuccess) return -(int)e;
-  const uint32_t W = lsmk_stream_waves(ncu);
+  const uint32_t W = stream_slices(ncu, n);
   if (!trusted) {  // a caller's batch: checked first, the cuts computed inside the check
     const bool vec = ((uintptr_t)P->off % 16u == 0) && ((uintptr_t)P->len % 16u == 0);
     const uint64_t nb = std::max<uint64_t>((n + 1023) / 1024, (W + 1u + 255u) / 256u);
@@ -1737,10 +1844,32 @@ extern "C" int lsmk_launch_crc32_stream(const CrcParams* P, int ncu, int variant
   const size_t lds = LDS_SCRATCH_OFF + LDS_SMAP_BYTES;
   e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return -(int)e;
-  void* args[] = {(void*)P};
+  CrcParams Q = *P;
+  Q.nslice = W;
+  Q.nwaves = (uint32_t)ncu * 16u;
+  void* args[] = {(void*)&Q};
   e = hipLaunchKernel(fn, dim3(ncu), dim3(1024), args, lds, st);
   if (e != hipSuccess) return -(int)e;
   e = hipGetLastError();
+#ifdef LSMCK_WAVE_DIAG
+  // append this launch's marks to the file LSMCK_WAVE_DIAG_OUT names: a header
+  // {magic, waves, records, 0} and four u64 per wave (waits for the launch)
+  if (const char* path = getenv("LSMCK_WAVE_DIAG_OUT")) {
+    const uint32_t nw = std::min<uint32_t>((uint32_t)ncu * 16u, LSMCK_WAVE_DIAG_MAX);
+    std::vector<uint64_t> h(4u * (nw + 1u));
+    h[0] = 0x4741494445564157ull;
+    h[1] = nw;
+    h[2] = n;
+    h[3] = 0;
+    if (hipStreamSynchronize(st) == hipSuccess &&
+        hipMemcpyFromSymbol(h.data() + 4, HIP_SYMBOL(g_wave_diag), 32u * nw) == hipSuccess) {
+      if (FILE* f = fopen(path, "ab")) {
+        fwrite(h.data(), 8, h.size(), f);
+        fclose(f);
+      }
+    }
+  }
+#endif
   return e == hipSuccess ? 0 : -(int)e;
 }
 

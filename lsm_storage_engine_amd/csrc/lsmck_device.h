@@ -27,7 +27,9 @@ struct CrcParams {
   const uint32_t* zero;       // 256 zero bytes (16-aligned): the load window of empty segments
   const uint64_t* sb_prefix;  // walking descriptor kernel: exclusive segment prefix per WALK_SB-record superblock
   uint32_t* sflag;            // stream kernel: nonzero = it takes the batch (the walking kernel then exits)
-  uint64_t* scuts;            // stream kernel: first record of each wave's range (waves + 1 entries)
+  uint64_t* scuts;            // stream kernel: first record of each slice (slices + 1 entries)
+  uint32_t nslice;            // stream kernel: slices of this launch (set by its launcher)
+  uint32_t nwaves;            // stream kernel: waves of this launch (set by its launcher)
 };
 
 // SHA-256 batch job (lane per message).
@@ -73,8 +75,9 @@ uint64_t lsmk_walk_sb_count(uint64_t n);
 int lsmk_launch_crc32_walk(const lsmck::CrcParams* P, uint64_t* sb_prefix, int ncu, int variant, hipStream_t st);
 // stream kernel for sorted, non-overlapping batches (packed or with small gaps;
 // a caller's batch is checked on the device unless `trusted`: P->sflag;
-// P->scuts holds lsmk_stream_waves(ncu) + 1 entries)
-uint32_t lsmk_stream_waves(int ncu);
+// P->sflag holds two u32, the flag and the slice tickets; P->scuts holds
+// lsmk_stream_slices_max(ncu) + 1 entries)
+uint32_t lsmk_stream_slices_max(int ncu);
 int lsmk_ab_ablations(void);  // 1: built with -DLSMCK_AB_ABLATIONS (tools/build_ab.sh)
 int lsmk_launch_crc32_stream(const lsmck::CrcParams* P, int ncu, int variant, int trusted, hipStream_t st);
 uint64_t lsmk_wal_words(uint64_t n);
