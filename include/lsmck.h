@@ -285,6 +285,10 @@ int lsmck_device_count(void);
  *                 "wal_encode_time": 1 = lsmck_sstable_encode_batch records
  *                 device events around its stages (tools/sst_encode_big.py
  *                 reads them back as stats); 0 = none (default).
+ *   "mem_build_time"  DIAGNOSTIC, not part of the stable option list, as
+ *                 "wal_encode_time": 1 = lsmck_memtable_build records device
+ *                 events around its stages (tools/memtable_big.py reads them
+ *                 back as stats); 0 = none (default).
  * Returns 0, or LSMCK_EINVAL for an unknown key / value. */
 int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value);
 
@@ -318,6 +322,15 @@ int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value);
  *                    stages between device events, with "sst_encode_time" 1:
  *                    sizes / order / index plan / spans, the data gather, the
  *                    index writer, the two digest passes.
+ *   "mem_rounds"     the chunk rounds the last lsmck_memtable_build ran (0 for
+ *                    fewer than two commands; each round is a host round trip).
+ *   "mem_validate_ns", "mem_chunk_ns", "mem_sort_ns", "mem_resolve_ns"
+ *                    DIAGNOSTIC, subject to change: the last
+ *                    lsmck_memtable_build's stages between device events, with
+ *                    "mem_build_time" 1: validate; the kernel that reads key
+ *                    bytes, summed over the rounds; the rounds' fixed-width
+ *                    part (sort passes, regroup, compaction), summed; resolve
+ *                    and emit.
  * Returns 0 and *value, or LSMCK_EINVAL for an unknown key. */
 int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value);
 
@@ -566,6 +579,67 @@ int lsmck_sstable_encode_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_
  * vlen > 2^32-1) or table_first is malformed. */
 int lsmck_sstable_encoded_size(const lsmck_wal_cmd* ents, size_t n, const uint64_t* table_first, size_t ntab,
                                uint64_t* data_bytes, uint64_t* index_bytes);
+
+/* Batch memtable build: the batch form of MemTable::from_log's map
+ * (src/memtable.rs:28-47) -- the step between the replay's records and
+ * lsmck_sstable_encode_batch's sorted entries, for a log replayed on the GPU,
+ * a group commit, several memtables flushed together or a bulk load.
+ * Commands 0..n-1 are in log order (type 1 Insert, 2 Remove; arenas and ranges
+ * as in lsmck_wal_encode_batch; a Remove's val_off and vlen are not looked at;
+ * keys and vals may be one buffer).  ents[0 .. *nent) receives the live
+ * entries as lsmck_wal_cmd of type 1, reserved 0, their ranges still pointing
+ * into the caller's arenas, strictly increasing in the reference's
+ * BTreeMap<Vec<u8>, _> order (bytewise, unsigned, a proper prefix first): per
+ * distinct key the LAST command in log order when that is an Insert, nothing
+ * when it is a Remove.  The array can be handed to lsmck_sstable_encode_batch
+ * as it is.  src (optional): src[j] = the index in cmds of the command ents[j]
+ * came from.  *mem_bytes = the reference's size_in_bytes() after from_log,
+ * its quirk included: from_log adds klen + vlen for every Insert, also one
+ * that overwrites (memtable.rs:37-38), and takes klen + vlen(current value)
+ * away for a Remove that finds its key.
+ * On the device (lsmck_memtable.hip, lsmck_memsort.h): the commands are
+ * validated; the order is refined 8 key bytes a round -- the elements still
+ * undecided sorted stably by (group, key bytes [8r, 8r+8) big-endian and zero
+ * padded, min(klen - 8r, 9)) with a radix sort of fixed-width words, runs of
+ * equal triples becoming the next round's groups, until no run of two or more
+ * unfinished keys is left; the last element of each run of equal keys is the
+ * key's last writer.  A pair of keys is separated in round lcp / 8, n copies
+ * of a key of l bytes take about l / 8 rounds, and every round costs a host
+ * round trip of 8 bytes (stat "mem_rounds"): keys of tens of bytes need 2-4
+ * rounds, many copies of a key of several KiB need hundreds.
+ * flags: LSMCK_DEVICE -- keys, vals, cmds (8-byte aligned), ents and src are
+ * device pointers; LSMCK_HOST (optionally | LSMCK_HOST_PINNED, a hint only) --
+ * host pointers, staged whole as lsmck_wal_encode_batch's host form is.  Any
+ * other flag bit is LSMCK_EINVAL.  nent, mem_bytes and bad_index are host
+ * pointers either way (nent and mem_bytes must not be NULL).  ents must not
+ * overlap cmds.  Synchronous; scratch comes from the context, so calls on one
+ * context serialise.  n >= 2^32 is LSMCK_EINVAL.
+ * Returns 0 (n == 0: no entries, 0 bytes), or
+ *   LSMCK_EINVAL  with *bad_index = the first offending command in batch
+ *                 order: a type other than 1 or 2, or a non-empty key, or a
+ *                 non-empty value of an Insert, outside its arena.
+ *   LSMCK_ENOSPC  cap < *nent: *nent is the count needed, *mem_bytes is set.
+ *   LSMCK_ENODEV  there is no GPU (and so no context).
+ * On any error no byte of ents or src is written. */
+int lsmck_memtable_build(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes, const uint8_t* vals,
+                         size_t vals_bytes, const lsmck_wal_cmd* cmds, size_t n, lsmck_wal_cmd* ents, size_t cap,
+                         uint32_t* src, size_t* nent, uint64_t* mem_bytes, uint64_t* bad_index, unsigned flags);
+
+/* The replay's compact records (lsmck_wal_replay_verify16 with
+ * LSMCK_RECS_DEVICE) as commands for lsmck_memtable_build, whose arenas are
+ * the log image itself (keys == vals == the image, img_bytes long): key_off =
+ * the payload offset, val_off = key_off + klen, type from bit 63, reserved 0.
+ * The payload the reference read is short at the end of the log
+ * (take().read_to_end, wal.rs:129-132): an Insert whose key lies wholly inside
+ * the image has vlen cut to what the image holds, a Remove its klen.  An
+ * Insert whose key is longer than the payload read (a key cut at the end of
+ * the log, or a u32 wrap of klen + vlen) keeps a key that reaches past
+ * img_bytes, so that the build reports LSMCK_EINVAL at that index: where the
+ * reference's split_off panics (wal.rs:142).  recs and cmds are device
+ * pointers; asynchronous on `stream` (NULL = the context's stream).  Returns
+ * 0, a negative hipError_t code, or LSMCK_ENODEV without a GPU. */
+int lsmck_wal_recs_to_cmds(lsmck_ctx* ctx, const lsmck_wal_rec16* recs, size_t n, uint64_t img_bytes,
+                           lsmck_wal_cmd* cmds, void* stream);
 
 /* Whole-tree SSTable verify: the batch form of Checksums::verify over many
  * tables (Db::load, src/tokio/db.rs:37-59 -> src/tokio/sstable.rs:34).

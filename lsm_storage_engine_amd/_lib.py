@@ -145,6 +145,9 @@ SIGNATURES = [
     ("lsmck_sstable_encode_batch", C.c_int,  # ents: lsmck_wal_cmd[n]; table_first: host u64[ntab + 1]
      [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, vp, vp, C.POINTER(sz), C.POINTER(sz), u64p, C.c_uint]),
     ("lsmck_sstable_encoded_size", C.c_int, [vp, sz, vp, sz, u64p, u64p]),
+    ("lsmck_memtable_build", C.c_int,  # cmds: lsmck_wal_cmd[n]; ents: lsmck_wal_cmd[cap]; src: u32[cap]
+     [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, C.POINTER(sz), u64p, u64p, C.c_uint]),
+    ("lsmck_wal_recs_to_cmds", C.c_int, [vp, vp, sz, C.c_uint64, vp, vp]),  # recs: lsmck_wal_rec16[n]
     ("lsmck_checksums_verify_many", C.c_int,
      [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), sz, C.POINTER(C.c_int)]),
     ("lsmck_tree_verify", C.c_int, [vp, C.c_char_p, C.POINTER(TreeReport)]),

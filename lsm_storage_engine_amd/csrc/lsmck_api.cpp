@@ -475,6 +475,32 @@ struct lsmck_ctx {
   bool sst_time = false;           // option "sst_encode_time": the encode's stages between device events
   long sst_ns[4] = {0, 0, 0, 0};   // the last timed encode: scan / order / plan, gather, index writer, digests
   hipEvent_t sst_ev[6] = {};       // (created by the first timed encode)
+  // batch memtable build (lsmck_memtable_build; grow-only, under mu): the
+  // workspace lsmk_mem_carve cuts into arrays, rocPRIM's temporary storage,
+  // the call's four words (the first invalid command, the round's active
+  // count, mem_bytes, the live entries) and their pinned copy; host form: the
+  // uploaded arenas and commands, the entries and their sources
+  struct {
+    uint8_t* ws = nullptr;
+    size_t cap_ws = 0;
+    uint8_t* tmp = nullptr;
+    size_t cap_tmp = 0;
+    unsigned long long* info = nullptr;
+    size_t cap_info = 0;
+    unsigned long long* h_info = nullptr;  // pinned
+    uint8_t* keys = nullptr;  // (the key arena alone: no kernel reads a value)
+    size_t cap_keys = 0;
+    lsmck_wal_cmd* cmds = nullptr;
+    size_t cap_cmds = 0;
+    lsmck_wal_cmd* ents = nullptr;
+    size_t cap_ents = 0;
+    uint32_t* src = nullptr;
+    size_t cap_src = 0;
+  } mem;
+  bool mem_time = false;           // option "mem_build_time": the build's stages between device events
+  long mem_ns[4] = {0, 0, 0, 0};   // the last timed build: validate, mem_chunk, the rounds' fixed-width part, resolve / emit
+  long mem_rounds = 0;             // the last build's rounds
+  hipEvent_t mem_ev[7] = {};       // (created by the first timed build)
   bool wal_recs_direct = false;  // this replay's records go by DMA into the caller's pinned array (under wal_mu)
   bool wal_compact = false;      // this replay's records are lsmck_wal_rec16 (under wal_mu)
   // LSMCK_RECS_DEVICE (under wal_mu): the caller's device array and its capacity
@@ -1341,6 +1367,12 @@ int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value) {
     ctx->sst_time = value != 0;
     return 0;
   }
+  if (!strcmp(key, "mem_build_time")) {  // diagnostic: lsmck_memtable_build's stages between device events
+    if (value != 0 && value != 1) return lsmck_host::set_error(LSMCK_EINVAL, "mem_build_time must be 0 or 1");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->mem_time = value != 0;
+    return 0;
+  }
   return lsmck_host::set_error(LSMCK_EINVAL, "unknown option");
 }
 
@@ -1385,6 +1417,16 @@ int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value) {
     *value = ctx->sst_ns[2];
   } else if (!strcmp(key, "sst_encode_sha_ns")) {
     *value = ctx->sst_ns[3];
+  } else if (!strcmp(key, "mem_rounds")) {  // the last lsmck_memtable_build's chunk rounds
+    *value = ctx->mem_rounds;
+  } else if (!strcmp(key, "mem_validate_ns")) {  // the last timed build's stages ("mem_build_time")
+    *value = ctx->mem_ns[0];
+  } else if (!strcmp(key, "mem_chunk_ns")) {
+    *value = ctx->mem_ns[1];
+  } else if (!strcmp(key, "mem_sort_ns")) {
+    *value = ctx->mem_ns[2];
+  } else if (!strcmp(key, "mem_resolve_ns")) {
+    *value = ctx->mem_ns[3];
   } else {
     return lsmck_host::set_error(LSMCK_EINVAL, "unknown stat");
   }
@@ -1434,6 +1476,15 @@ void lsmck_ctx_destroy(lsmck_ctx* ctx) {
       if (p) (void)hipFree(p);
   }
   for (hipEvent_t e : ctx->sst_ev)
+    if (e) (void)hipEventDestroy(e);
+  {
+    auto& M = ctx->mem;
+    for (void* p : {(void*)M.ws, (void*)M.tmp, (void*)M.info, (void*)M.keys, (void*)M.cmds,
+                    (void*)M.ents, (void*)M.src})
+      if (p) (void)hipFree(p);
+    if (M.h_info) host_free(M.h_info);
+  }
+  for (hipEvent_t e : ctx->mem_ev)
     if (e) (void)hipEventDestroy(e);
   if (ctx->h_verify) host_free(ctx->h_verify);
   if (ctx->h_wrecs) host_free(ctx->h_wrecs);
@@ -2839,6 +2890,152 @@ int lsmck_sstable_encode_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_
     }
   }
   return 0;
+}
+
+// the two memtable calls without a context: there is none without a GPU
+static int mem_no_ctx(const char* what) {
+  if (lsmck_device_count() <= 0)
+    return lsmck_host::set_error(LSMCK_ENODEV, (std::string(what) + ": no HIP device available, so no context").c_str());
+  return lsmck_host::set_error(LSMCK_EINVAL, "null context");
+}
+
+int lsmck_memtable_build(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes, const uint8_t* vals,
+                         size_t vals_bytes, const lsmck_wal_cmd* cmds, size_t n, lsmck_wal_cmd* ents, size_t cap,
+                         uint32_t* src, size_t* nent, uint64_t* mem_bytes, uint64_t* bad_index, unsigned flags) {
+  if (nent) *nent = 0;
+  if (mem_bytes) *mem_bytes = 0;
+  if (bad_index) *bad_index = ~0ull;
+  if (!nent || !mem_bytes) return lsmck_host::set_error(LSMCK_EINVAL, "memtable build: null nent or mem_bytes");
+  if (flags & ~(LSMCK_DEVICE | LSMCK_HOST_PINNED))
+    return lsmck_host::set_error(LSMCK_EINVAL, "memtable build: unknown flag");
+  if (n >= (1ull << 32))
+    return lsmck_host::set_error(LSMCK_EINVAL, "memtable build: more than 2^32-1 commands in one batch");
+  if (!ctx) return mem_no_ctx("memtable build");
+  if (n == 0) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->mem_rounds = 0;
+    return 0;
+  }
+  if (!cmds) return lsmck_host::set_error(LSMCK_EINVAL, "null commands");
+  int rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DevGuard g(ctx->dev);
+  const hipStream_t st = ctx->stream0;
+  ScratchOrder so(ctx, st);
+  if (so.e != hipSuccess) return hip_error(so.e, "hipStreamWaitEvent(scratch)");
+  auto& M = ctx->mem;
+  const bool dev = (flags & LSMCK_DEVICE) != 0;
+  const uint8_t* dk = keys;
+  const lsmck_wal_cmd* dc = cmds;
+  if (!dev) {  // staged whole: the key arena and the commands (no kernel reads a value)
+    if ((rc = ensure_dev(&M.keys, &M.cap_keys, keys_bytes)) || (rc = ensure_dev(&M.cmds, &M.cap_cmds, n))) return rc;
+    if (keys_bytes) HIPCHK(hipMemcpyAsync(M.keys, keys, keys_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(M.cmds, cmds, n * sizeof(lsmck_wal_cmd), hipMemcpyHostToDevice, st));
+    dk = M.keys;
+    dc = M.cmds;
+  }
+  lsmck::MemWs W;
+  if ((rc = ensure_dev(&M.ws, &M.cap_ws, lsmk_mem_carve(nullptr, n, nullptr))) ||
+      (rc = ensure_dev(&M.info, &M.cap_info, 4)))
+    return rc;
+  if (!M.h_info) HIPCHK(hipHostMalloc((void**)&M.h_info, 64, hipHostMallocDefault));
+  (void)lsmk_mem_carve(M.ws, n, &W);
+  const bool timed = ctx->mem_time;
+  hipEvent_t* ev = ctx->mem_ev;
+  if (timed && !ev[0])
+    for (int k = 0; k < 7; ++k) HIPCHK(hipEventCreate(&ev[k]));
+  double ns[4] = {0, 0, 0, 0};
+  auto span = [&](int a, int b, double* into) -> int {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ev[a], ev[b]));
+    *into += (double)ms * 1e6;
+    return 0;
+  };
+  // 1. validate; its word comes back before any kernel reads a key
+  unsigned long long* info = M.info;  // [0] first invalid, [1] active count, [2] mem_bytes
+  HIPCHK(hipMemsetAsync(info, 0xFF, 8, st));
+  HIPCHK(hipMemsetAsync(info + 1, 0, 16, st));
+  if (timed) HIPCHK(hipEventRecord(ev[0], st));
+  if ((rc = lsmk_mem_validate(dc, n, keys_bytes, vals_bytes, info, st))) return launch_rc(rc, "memtable validate kernel");
+  if (timed) HIPCHK(hipEventRecord(ev[1], st));
+  HIPCHK(hipMemcpyAsync(M.h_info, info, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (timed && (rc = span(0, 1, &ns[0]))) return rc;
+  if (M.h_info[0] != ~0ull) {
+    if (bad_index) *bad_index = M.h_info[0];
+    return lsmck_host::set_error(LSMCK_EINVAL, "memtable build: invalid command (type or source range)");
+  }
+  // 2. the rounds
+  if ((rc = lsmk_mem_init(&W, n, st))) return launch_rc(rc, "memtable init kernel");
+  unsigned group_bits = 1;
+  while (group_bits < 32 && ((uint64_t)1 << group_bits) < n) ++group_bits;
+  uint64_t m = n >= 2 ? n : 0;
+  long rounds = 0;
+  for (uint64_t r = 0; m; ++r, ++rounds) {
+    size_t tmp = 0;
+    if ((rc = lsmk_mem_sort_regroup(&W, m, r, group_bits, nullptr, &tmp, nullptr, st)))
+      return launch_rc(rc, "memtable sort (temporary storage size)");
+    if ((rc = ensure_dev(&M.tmp, &M.cap_tmp, tmp))) return rc;
+    if (timed) HIPCHK(hipEventRecord(ev[2], st));
+    if ((rc = lsmk_mem_chunk(&W, dk, dc, m, r, st))) return launch_rc(rc, "memtable chunk kernel");
+    if (timed) HIPCHK(hipEventRecord(ev[3], st));
+    tmp = M.cap_tmp;
+    if ((rc = lsmk_mem_sort_regroup(&W, m, r, group_bits, M.tmp, &tmp, info + 1, st)))
+      return launch_rc(rc, "memtable sort / regroup kernels");
+    if (timed) HIPCHK(hipEventRecord(ev[4], st));
+    HIPCHK(hipMemcpyAsync(M.h_info + 1, info + 1, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (timed && ((rc = span(2, 3, &ns[1])) || (rc = span(3, 4, &ns[2])))) return rc;
+    if (M.h_info[1] > m) return lsmck_host::set_error(LSMCK_EIO, "memtable build: active count grew");
+    m = M.h_info[1];
+    std::swap(W.apos, W.apos2);
+  }
+  ctx->mem_rounds = rounds;
+  // 3. resolve; the count and the bytes come back before ents and src are written
+  size_t tmp = 0;
+  if ((rc = lsmk_mem_resolve(&W, dc, n, nullptr, &tmp, nullptr, st))) return launch_rc(rc, "memtable scan (size)");
+  if ((rc = ensure_dev(&M.tmp, &M.cap_tmp, tmp))) return rc;
+  tmp = M.cap_tmp;
+  if (timed) HIPCHK(hipEventRecord(ev[5], st));
+  if ((rc = lsmk_mem_resolve(&W, dc, n, M.tmp, &tmp, info + 2, st))) return launch_rc(rc, "memtable resolve kernels");
+  M.h_info[3] = 0;
+  HIPCHK(hipMemcpyAsync(M.h_info + 2, info + 2, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(M.h_info + 3, W.ex + n, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const uint64_t live = M.h_info[3];
+  *mem_bytes = M.h_info[2];
+  *nent = (size_t)live;
+  if (cap < live) return lsmck_host::set_error(LSMCK_ENOSPC, "memtable build: cap is smaller than the live entries");
+  if (live && !ents) return lsmck_host::set_error(LSMCK_EINVAL, "null ents");
+  lsmck_wal_cmd* de = ents;
+  uint32_t* ds = src;
+  if (!dev && live) {
+    if ((rc = ensure_dev(&M.ents, &M.cap_ents, (size_t)live)) || (src && (rc = ensure_dev(&M.src, &M.cap_src, (size_t)live))))
+      return rc;
+    de = M.ents;
+    ds = src ? M.src : nullptr;
+  }
+  if (live && (rc = lsmk_mem_emit(&W, dc, n, de, ds, st))) return launch_rc(rc, "memtable emit kernel");
+  if (timed) HIPCHK(hipEventRecord(ev[6], st));
+  if (!dev && live) {
+    HIPCHK(hipMemcpyAsync(ents, de, (size_t)live * sizeof(lsmck_wal_cmd), hipMemcpyDeviceToHost, st));
+    if (src) HIPCHK(hipMemcpyAsync(src, ds, (size_t)live * 4, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  if (timed) {
+    if ((rc = span(5, 6, &ns[3]))) return rc;
+    for (int k = 0; k < 4; ++k) ctx->mem_ns[k] = (long)ns[k];
+  }
+  return 0;
+}
+
+int lsmck_wal_recs_to_cmds(lsmck_ctx* ctx, const lsmck_wal_rec16* recs, size_t n, uint64_t img_bytes,
+                           lsmck_wal_cmd* cmds, void* stream) {
+  if (!ctx) return mem_no_ctx("wal_recs_to_cmds");
+  if (n == 0) return 0;
+  if (!recs || !cmds) return lsmck_host::set_error(LSMCK_EINVAL, "null records or commands");
+  DevGuard g(ctx->dev);
+  return launch_rc(lsmk_mem_recs_to_cmds(recs, n, img_bytes, cmds, pick_stream(ctx, stream)), "wal_recs_to_cmds kernel");
 }
 
 }  // extern "C"

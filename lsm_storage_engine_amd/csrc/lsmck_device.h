@@ -65,9 +65,39 @@ struct ShaSliceParams {
   unsigned char* out;
 };
 
+// The batch memtable build's workspace (lsmck_memtable.hip; carved out of one
+// allocation by lsmk_mem_carve).  Per position of the order: perm (the
+// command there), grp (its group's head position), head (its key differs from
+// its predecessor's).  Per active slot of a round: apos (its position; apos2
+// the next round's), chunk / tail / g / idx (the element's sort fields and
+// command), o1..o3 (the slots' order after each sort pass), kout (the passes'
+// sorted keys, unused), bnd / hd (run starts and their max-scan), act / ex
+// (flags and their exclusive scan: the round's still-active slots; at the end
+// the live positions and their output slots, n + 1 entries).
+struct MemWs {
+  uint64_t *chunk, *kout;
+  uint32_t *perm, *grp, *apos, *apos2, *g, *idx, *o1, *o2, *o3, *bnd, *hd, *act, *ex;
+  uint8_t *tail, *head;
+};
+
 }  // namespace lsmck
 
 extern "C" {
+// batch memtable build (lsmck_memtable_build; lsmck_memtable.hip mem_*)
+size_t lsmk_mem_carve(uint8_t* ws, uint64_t n, lsmck::MemWs* W);
+int lsmk_mem_validate(const lsmck_wal_cmd* cmds, uint64_t n, uint64_t keys_bytes, uint64_t vals_bytes,
+                      unsigned long long* info, hipStream_t st);
+int lsmk_mem_init(const lsmck::MemWs* W, uint64_t n, hipStream_t st);
+int lsmk_mem_chunk(const lsmck::MemWs* W, const uint8_t* keys, const lsmck_wal_cmd* cmds, uint64_t m, uint64_t r,
+                   hipStream_t st);
+int lsmk_mem_sort_regroup(const lsmck::MemWs* W, uint64_t m, uint64_t r, unsigned group_bits, void* tmp,
+                          size_t* tmp_bytes, unsigned long long* count, hipStream_t st);
+int lsmk_mem_resolve(const lsmck::MemWs* W, const lsmck_wal_cmd* cmds, uint64_t n, void* tmp, size_t* tmp_bytes,
+                     unsigned long long* bytes, hipStream_t st);
+int lsmk_mem_emit(const lsmck::MemWs* W, const lsmck_wal_cmd* cmds, uint64_t n, lsmck_wal_cmd* ents, uint32_t* src,
+                  hipStream_t st);
+int lsmk_mem_recs_to_cmds(const lsmck_wal_rec16* recs, uint64_t n, uint64_t img_bytes, lsmck_wal_cmd* cmds,
+                          hipStream_t st);
 int lsmk_launch_crc32_fixed(const lsmck::CrcParams* P, int ncu, int variant, hipStream_t st);
 int lsmk_launch_sha256(const lsmck::ShaParams* P, hipStream_t st);
 int lsmk_launch_sha256_slices(const lsmck::ShaSliceParams* P, hipStream_t st);

@@ -115,6 +115,17 @@ class SstEncodeError(_lib.LsmckError):
         super().__init__(rc, f"{what} (bad_index={bad_index}, needed={needed})")
 
 
+class MemBuildError(_lib.LsmckError):
+    """lsmck_memtable_build refused the batch: ``bad_index`` is the first
+    invalid command (LSMCK_EINVAL), or ``needed`` the live entries' count when
+    the array given holds fewer (LSMCK_ENOSPC); the other one is None."""
+
+    def __init__(self, rc, what, bad_index=None, needed=None):
+        self.bad_index = bad_index
+        self.needed = needed
+        super().__init__(rc, f"{what} (bad_index={bad_index}, needed={needed})")
+
+
 class Context:
     def __init__(self, device=0):
         lib = _lib.load()
@@ -384,6 +395,54 @@ class Context:
         nothing was written then."""
         return self._sst_encode(keys_ptr, keys_bytes, vals_ptr, vals_bytes, ents_ptr, n, table_first, data_ptr,
                                 data_cap, index_ptr, index_cap, spans_ptr, data_sha_ptr, index_sha_ptr, _lib.DEVICE)
+
+    def _mem_build(self, keys, kb, vals, vb, cmds, n, ents, cap, src, flags):
+        none = 2 ** 64 - 1
+        nent, nbytes, bad = C.c_size_t(), C.c_uint64(), C.c_uint64(none)
+        rc = self.lib.lsmck_memtable_build(self.handle, keys, kb, vals, vb, cmds, n, ents, cap, src, C.byref(nent),
+                                           C.byref(nbytes), C.byref(bad), flags)
+        if rc == _lib.EINVAL and bad.value != none:
+            raise MemBuildError(rc, "memtable_build", bad_index=bad.value)
+        if rc == _lib.ENOSPC:
+            raise MemBuildError(rc, "memtable_build", needed=nent.value)
+        _lib.check(rc, "memtable_build")
+        return nent.value, nbytes.value
+
+    def memtable_build(self, keys, vals, cmds, pinned=False):
+        """lsmck_memtable_build, host form: the memtable of the commands
+        ``cmds`` (WAL_CMD_DTYPE in log order: key / value ranges in the uint8
+        arenas ``keys`` / ``vals``, which may be one array), sorted and
+        resolved on the GPU.  Returns (ents: WAL_CMD_DTYPE, the live entries
+        in key order, their ranges in the same arenas; src: np.uint32, the
+        command each came from; mem_bytes: the reference's size_in_bytes()).
+        Raises MemBuildError (``bad_index``: the first invalid command)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint8)
+        vals = keys if vals is keys else np.ascontiguousarray(vals, dtype=np.uint8)
+        cmds = np.ascontiguousarray(cmds, dtype=_lib.WAL_CMD_DTYPE)
+        n = len(cmds)
+        ents = np.empty(n, dtype=_lib.WAL_CMD_DTYPE)  # (at most every command is live)
+        src = np.empty(n, dtype=np.uint32)
+        flags = _lib.HOST_PINNED if pinned else _lib.HOST
+        nent, nbytes = self._mem_build(keys.ctypes.data, keys.nbytes, vals.ctypes.data, vals.nbytes, cmds.ctypes.data,
+                                       n, ents.ctypes.data, n, src.ctypes.data, flags)
+        return ents[:nent], src[:nent], nbytes
+
+    def memtable_build_device(self, keys_ptr, keys_bytes, vals_ptr, vals_bytes, cmds_ptr, n, ents_ptr, cap,
+                              src_ptr=None):
+        """lsmck_memtable_build on device pointers (cmds: n lsmck_wal_cmd;
+        ents: cap lsmck_wal_cmd; src_ptr: cap u32 or None).  Returns (nent,
+        mem_bytes); raises MemBuildError with ``bad_index`` (an invalid
+        command) or ``needed`` (cap is smaller than the live entries' count);
+        nothing was written then."""
+        return self._mem_build(keys_ptr, keys_bytes, vals_ptr, vals_bytes, cmds_ptr, n, ents_ptr, cap, src_ptr,
+                               _lib.DEVICE)
+
+    def wal_recs_to_cmds_device(self, recs_ptr, n, img_bytes, cmds_ptr, stream=None):
+        """lsmck_wal_recs_to_cmds: n compact replay records (lsmck_wal_rec16,
+        device) as lsmck_wal_cmd (device) over the log image of img_bytes
+        bytes, keys == vals == the image.  Asynchronous on ``stream``."""
+        _lib.check(self.lib.lsmck_wal_recs_to_cmds(self.handle, recs_ptr, n, img_bytes, cmds_ptr, stream),
+                   "wal_recs_to_cmds")
 
     def wal_replay_verify(self, image, device_ptr=None, cap=None, pinned_recs=False, compact=False):
         """Returns (records, status, (bad_index, bad_crc, bad_expected)).

@@ -137,4 +137,40 @@ def from_memtable(base_path, memtable, ctx=None, timestamp_ms=None):
     return flush_many(base_path, 0, [memtable], ctx, ts)[0]
 
 
-__all__ = ["from_memtable", "flush_many", "table_bytes", "batch_arrays", "INDEX_STEP"]
+def flush_log_image(base_path, image, ctx, timestamp_ms=None):
+    """A log image as a level-0 table, the whole chain on the device: replay,
+    commands, memtable build (wal.device_memtable), then
+    lsmck_sstable_encode_batch over the live entries with keys = vals = the
+    image.  Only the data file, the index file and the two digests come back;
+    no record or entry visits the host.  The files equal
+    ``from_memtable(base_path, MemTable.from_log(CommandLog.new_in_memory(image)))``'s.
+    Returns the table's SsTableMetadata."""
+    from . import wal
+    from .device import SstEncodeError
+    d = wal.device_memtable(image, ctx)
+    bufs = []
+    try:
+        first = [0, d.nent]
+        args = (d.image.ptr, d.image_bytes, d.image.ptr, d.image_bytes, d.ents.ptr, d.nent, first)
+        try:  # the sizes: the index file holds its count at least, so no buffer at all is too small
+            ctx.sstable_encode_batch_device(*args, None, 0, None, 0)
+            raise AssertionError("an index file is never empty")
+        except SstEncodeError as e:
+            if e.needed is None:
+                raise
+            db, ib = e.needed
+        bufs = [ctx.alloc(max(db, 1)), ctx.alloc(ib), ctx.alloc(64)]
+        data, index, sha = bufs
+        got = ctx.sstable_encode_batch_device(*args, data.ptr, db, index.ptr, ib, None, sha.ptr, sha.ptr + 32)
+        assert got == (db, ib)
+        digests = sha.download(np.uint8, 64)
+        m = SsTableMetadata.new(str(base_path), 0, timestamp_ms=timestamp_ms)
+        return _write_table(m, data.download(np.uint8, db).data, index.download(np.uint8, ib).data, digests[32:],
+                            digests[:32])
+    finally:
+        d.free()
+        for b in bufs:
+            b.free()
+
+
+__all__ = ["from_memtable", "flush_many", "flush_log_image", "table_bytes", "batch_arrays", "INDEX_STEP"]

@@ -230,6 +230,65 @@ def _split_off_msg(at, length):
     return f"`at` split index (is {at}) should be <= len (is {length})"
 
 
+class DeviceMemTable:
+    """A log image's memtable left on the device: ``image`` (DeviceBuffer, the
+    arena of every range), ``ents`` (DeviceBuffer of ``nent`` lsmck_wal_cmd in
+    key order), ``mem_bytes``.  ``free()`` releases both buffers."""
+
+    def __init__(self, image, image_bytes, ents, nent, mem_bytes):
+        self.image, self.image_bytes, self.ents, self.nent, self.mem_bytes = image, image_bytes, ents, nent, mem_bytes
+
+    def free(self):
+        self.image.free()
+        self.ents.free()
+
+
+def device_memtable(image, ctx):
+    """The log image -> its memtable without a record visiting the host: the
+    image is uploaded, replayed with compact records left on the device
+    (lsmck_wal_replay_verify16, LSMCK_RECS_DEVICE), the records become
+    commands over the image (lsmck_wal_recs_to_cmds) and the commands the live
+    entries in key order (lsmck_memtable_build).  Raises what the iterator
+    raises first: a key cut at the end of the log (the build's LSMCK_EINVAL) is
+    the split_off ``WalPanic``, the replay's statuses are ``replay_verify``'s."""
+    from .device import MemBuildError, WAL_REC16_DTYPE
+    img = np.frombuffer(image, dtype=np.uint8) if len(image) else np.zeros(0, dtype=np.uint8)
+    n = len(img)
+    cap = n // 9 + 1
+    dimg, drecs = ctx.alloc(max(n, 1)), ctx.alloc(cap * 16)
+    dcmds = dents = None
+    try:
+        if n:
+            dimg.upload(img)
+        nrec, status, bad = ctx.wal_replay_verify_to_device(n, drecs.ptr, cap, device_ptr=dimg.ptr, compact=True)
+        dcmds, dents = ctx.alloc(max(nrec, 1) * 32), ctx.alloc(max(nrec, 1) * 32)
+        ctx.wal_recs_to_cmds_device(drecs.ptr, nrec, n, dcmds.ptr)
+        try:  # (the accepted records of a log that ends in an error too: a panic among them comes first)
+            nent, nbytes = ctx.memtable_build_device(dimg.ptr, n, dimg.ptr, n, dcmds.ptr, nrec, dents.ptr, nrec)
+        except MemBuildError as e:
+            if e.bad_index is None:
+                raise
+            r = drecs.download(WAL_REC16_DTYPE, 1, 16 * e.bad_index)[0]
+            k0, kl, vl = int(r["payload_type"]) & (_lib.WAL_REC16_REMOVE - 1), int(r["klen"]), int(r["vlen"])
+            raise WalPanic(_split_off_msg(kl, min((kl + vl) & 0xFFFFFFFF, max(n - k0, 0)))) from None
+        if status == _lib.WAL_CORRUPTED:
+            raise CorruptedData(bad[1], bad[2])
+        if status == _lib.WAL_REMOVE_PANIC:
+            raise WalPanic(f"data corruption encountered ({bad[1]:08x}) != {bad[2]:08x}")
+        if status == _lib.WAL_BAD_TYPE:
+            raise InvalidCommandType(bad[1])
+    except BaseException:
+        for b in (dimg, dents):
+            if b is not None:
+                b.free()
+        raise
+    finally:
+        drecs.free()
+        if dcmds is not None:
+            dcmds.free()
+    return DeviceMemTable(dimg, n, dents, nent, nbytes)
+
+
 class MemTable:
     """The replay consumer, src/memtable.rs:9-47 (BTreeMap + byte count)."""
 
@@ -249,6 +308,24 @@ class MemTable:
             else:
                 v = t.data.pop(rec.key, None)
                 t.bytes -= (len(v) + len(rec.key)) if v is not None else 0
+        return t
+
+    @classmethod
+    def from_image(cls, image, ctx):
+        """``from_log(CommandLog.new_in_memory(image))`` with the replay, the
+        sort and the last-writer-wins on the GPU (``device_memtable``): only
+        the live entries come back, and their bytes are taken from ``image``."""
+        d = device_memtable(image, ctx)
+        try:
+            ents = d.ents.download(_lib.WAL_CMD_DTYPE, d.nent)
+        finally:
+            d.free()
+        t = cls()
+        img = bytes(image)
+        for k0, kl, v0, vl in zip(ents["key_off"].tolist(), ents["klen"].tolist(), ents["val_off"].tolist(),
+                                  ents["vlen"].tolist()):
+            t.data[img[k0:k0 + kl]] = img[v0:v0 + vl]
+        t.bytes = d.mem_bytes
         return t
 
     def get(self, key):
