@@ -164,7 +164,7 @@ int lsmck_device_count(void);
  *   "crc_ablate"  DIAGNOSTIC ONLY, results are invalid while set: 3 = payload
  *                 loads only (ring, stream and walking kernels: the bench's
  *                 loads-only ceiling); 0 = off.  2 (the stream kernel without
- *                 payload loads) and 4..10 (stream kernel ablations,
+ *                 payload loads) and 4..12 (stream kernel ablations,
  *                 DESIGN.md 3.1 items 10-11) only in A/B builds
  *                 (-DLSMCK_AB_ABLATIONS, tools/build_ab.sh).
  *   "sha_order"   variable-length SHA-256 batches of >= 2048 messages run in
@@ -271,11 +271,9 @@ int lsmck_device_count(void);
  *                 CUs (default 32), "wal_pipe_layout" which ones (0 the last,
  *                 1 spread), "wal_pipe_seg" the parts' segment bytes (0 =
  *                 sized to the walk's CUs).  A/B; results are the same.
+ *   "wal_pipe_min"  the smallest log the pipeline takes, in bytes (>= 0).
  *   "tree_readers"  whole-tree verify: reader threads per context (default
  *                 16; 1..64).  A/B.
- *   "crc_ablate"  diagnostic: 3 = the stream kernel with payload loads only
- *                 (the bench's loads-only ceiling; results are garbage); 2,
- *                 4..12 only in A/B libraries built with -DLSMCK_AB_ABLATIONS.
  *   "wal_encode_time"  DIAGNOSTIC, not part of the stable option list (it and
  *                 its stats may change or go with the tool that uses them):
  *                 1 = lsmck_wal_encode_batch records device events around

@@ -37,9 +37,11 @@
 #include <unistd.h>
 
 #include "lsmck.h"
+#include "lsmck_buf.h"
 #include "lsmck_device.h"
 #include "lsmck_dma.h"
 #include "lsmck_internal.h"
+#include "lsmck_options.h"
 #include "lsmck_pool.h"
 #include "lsmck_segwalk.h"
 
@@ -49,8 +51,6 @@ using lsmck::ShaParams;
 namespace {
 
 constexpr uint64_t kMaxSegsPerLaunch = (1ull << 32) - 64;  // 32-bit segment indices in the kernels
-constexpr int kVariantNoStream = 0x200000;  // descriptor batches: no stream kernel for packed >= 64-byte records (A/B)
-constexpr int kVariantStreamOnly = 0x400000;  // diagnostic: the stream kernel alone (ineligible batches get no CRCs)
 constexpr size_t kChunkBytes = 64ull << 20;                // host staging chunk (payload)
 constexpr size_t kChunkRecs = 1u << 20;                    // host staging chunk (records)
 constexpr int kWalHostWalk = 0x7FFF0001;  // internal: the GPU header walk declined the log; walk it on the host
@@ -76,18 +76,6 @@ int launch_rc(int rc, const char* what) {
   return hip_error((hipError_t)(-rc), what);
 }
 
-template <typename T>
-int ensure_dev(T** p, size_t* cap, size_t need) {
-  if (*cap >= need && *p) return 0;
-  size_t want = std::max(need, *cap * 3 / 2);
-  if (want == 0) want = 1;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  HIPCHK(hipMalloc((void**)p, want * sizeof(T)));
-  *cap = want;
-  return 0;
-}
 
 // --- NUMA: the staging buffers and threads next to the device --
 // On a node with several sockets each GPU hangs off one socket's PCIe root;
@@ -227,64 +215,46 @@ hipError_t host_malloc_near(void** p, size_t bytes, int node, bool huge = false)
   return e;
 }
 
+// The allocators of the context's buffers (lsmck_buf.h).  A failure's message
+// goes to lsmck_last_error() only through fail(): the try_ forms leave it alone.
+struct HipAlloc {
+  using err_t = hipError_t;
+  static bool ok(hipError_t e) { return e == hipSuccess; }
+};
+struct DevAlloc : HipAlloc {
+  static hipError_t alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+  static void free(void* p) { (void)hipFree(p); }
+  static hipError_t copy(void* dst, const void* src, size_t bytes, hipStream_t st) {
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st);
+    return e != hipSuccess ? e : hipStreamSynchronize(st);
+  }
+  static int fail(hipError_t e) { return hip_error(e, "hipMalloc (device buffer)"); }
+};
+// pinned: ensure(need, node, huge) -- host_malloc_near's node and huge
+struct PinAlloc : HipAlloc {
+  static hipError_t alloc(void** p, size_t bytes, int node, bool huge = false) {
+    return host_malloc_near(p, bytes, node, huge);
+  }
+  static void free(void* p) { host_free(p); }
+  static int fail(hipError_t e) { return hip_error(e, "hipHostMalloc (pinned buffer)"); }
+};
 template <typename T>
-int ensure_pinned(int node, T** p, size_t* cap, size_t need, bool huge = false) {
-  if (*cap >= need && *p) return 0;
-  size_t want = std::max(need, *cap * 3 / 2);
-  if (want == 0) want = 1;
-  if (*p) host_free(*p);
-  *p = nullptr;
-  *cap = 0;
-  HIPCHK(host_malloc_near((void**)p, want * sizeof(T), node, huge));
-  *cap = want;
-  return 0;
-}
-
-// ensure_dev that keeps the first `keep` elements (copied on st)
+using DevBuf = lsmck_host::GrowBuf<T, DevAlloc>;
 template <typename T>
-int ensure_dev_keep(T** p, size_t* cap, size_t need, size_t keep, hipStream_t st) {
-  if (*cap >= need && *p) return 0;
-  if (!keep || !*p) return ensure_dev(p, cap, need);
-  const size_t want = std::max(need, *cap * 3 / 2);
-  T* q = nullptr;
-  HIPCHK(hipMalloc((void**)&q, want * sizeof(T)));
-  HIPCHK(hipMemcpyAsync(q, *p, keep * sizeof(T), hipMemcpyDeviceToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));
-  (void)hipFree(*p);
-  *p = q;
-  *cap = want;
-  return 0;
-}
+using PinBuf = lsmck_host::GrowBuf<T, PinAlloc>;
 
 // Scratch of the descriptor CRC path (one per in-flight launch).
 struct DescScratch {
-  uint64_t* block_sum = nullptr;  // per 1024-record block
-  size_t cap_bs = 0;
-  uint64_t* total = nullptr;  // device, 1 u64
+  DevBuf<uint64_t> block_sum;  // per 1024-record block
+  DevBuf<uint64_t> total;      // 2 u64
   // SHA-256 dispatch order (lsmck_order.hip)
-  uint16_t* sha_keys = nullptr;
-  size_t cap_keys = 0;
-  uint32_t* sha_order = nullptr;
-  size_t cap_order = 0;
-  unsigned char* sort_tmp = nullptr;
-  size_t cap_tmp = 0;
-  uint64_t* sha_split = nullptr;  // device, 1 u64: where the order's short tail starts
-  size_t cap_split = 0;
-  // stream kernel (lsmck_crc32.hip): eligibility flag, per-wave boundary cuts
-  uint32_t* sflag = nullptr;
-  uint64_t* scuts = nullptr;
-  size_t cap_cuts = 0;
-  void release() {
-    if (sflag) (void)hipFree(sflag);
-    if (scuts) (void)hipFree(scuts);
-    if (block_sum) (void)hipFree(block_sum);
-    if (total) (void)hipFree(total);
-    if (sha_keys) (void)hipFree(sha_keys);
-    if (sha_order) (void)hipFree(sha_order);
-    if (sort_tmp) (void)hipFree(sort_tmp);
-    if (sha_split) (void)hipFree(sha_split);
-    *this = DescScratch();
-  }
+  DevBuf<uint16_t> sha_keys;
+  DevBuf<uint32_t> sha_order;
+  DevBuf<unsigned char> sort_tmp;
+  DevBuf<uint64_t> sha_split;  // 1 u64: where the order's short tail starts
+  // stream kernel (lsmck_crc32.hip): eligibility flag (4 u32), per-wave boundary cuts
+  DevBuf<uint32_t> sflag;
+  DevBuf<uint64_t> scuts;
 };
 
 // One pinned staging slot of the host-resident pipeline.
@@ -292,215 +262,166 @@ struct Stage {
   hipStream_t s = nullptr;
   hipEvent_t done = nullptr;
   bool busy = false;
-  // host (pinned)
-  uint8_t* h_pay = nullptr;
-  size_t cap_h_pay = 0;
-  uint64_t* h_off = nullptr;
-  size_t cap_h_off = 0;
-  uint32_t* h_len = nullptr;
-  size_t cap_h_len = 0;
-  uint8_t* h_out = nullptr;
-  size_t cap_h_out = 0;
-  // device
-  uint8_t* d_pay = nullptr;
-  size_t cap_d_pay = 0;
-  uint64_t* d_off = nullptr;
-  size_t cap_d_off = 0;
-  uint32_t* d_len = nullptr;
-  size_t cap_d_len = 0;
-  uint8_t* d_out = nullptr;
-  size_t cap_d_out = 0;
+  PinBuf<uint8_t> h_pay;
+  PinBuf<uint64_t> h_off;
+  PinBuf<uint32_t> h_len;
+  PinBuf<uint8_t> h_out;
+  DevBuf<uint8_t> d_pay;
+  DevBuf<uint64_t> d_off;
+  DevBuf<uint32_t> d_len;
+  DevBuf<uint8_t> d_out;
   DescScratch scratch;
   // whole-tree verify: slice descriptors of the round in this slot
-  lsmck::ShaSlice* h_slices = nullptr;
-  size_t cap_h_slices = 0;
-  lsmck::ShaSlice* d_slices = nullptr;
-  size_t cap_d_slices = 0;
+  PinBuf<lsmck::ShaSlice> h_slices;
+  DevBuf<lsmck::ShaSlice> d_slices;
   // bookkeeping of the chunk in flight
   size_t rec0 = 0, nrec = 0;
-  void release() {
-    if (h_pay) host_free(h_pay);
-    if (h_off) host_free(h_off);
-    if (h_len) host_free(h_len);
-    if (h_out) host_free(h_out);
-    if (d_pay) (void)hipFree(d_pay);
-    if (d_off) (void)hipFree(d_off);
-    if (d_len) (void)hipFree(d_len);
-    if (d_out) (void)hipFree(d_out);
-    if (h_slices) host_free(h_slices);
-    if (d_slices) (void)hipFree(d_slices);
-    scratch.release();
+  ~Stage() {  // (with its context: lsmck_ctx_destroy)
     if (done) (void)hipEventDestroy(done);
     if (s) (void)hipStreamDestroy(s);
-    *this = Stage();
   }
 };
 constexpr int kHostSlots = 2;  // slots the host batches and the WAL upload alternate
 
 }  // namespace
 
+// A batch builder's stages between device events (its "*_time" option).  The
+// events are created when first recorded; the spans add up over the call and
+// become the stats only when it finishes.
+struct StageTimer {
+  hipEvent_t ev[7] = {};
+  double acc[4] = {0, 0, 0, 0};
+  long ns[4] = {0, 0, 0, 0};  // the last timed call's stages
+  bool on = false;            // this call is timed
+  void begin(bool timed) {
+    on = timed;
+    for (double& a : acc) a = 0;
+  }
+  hipError_t mark(int k, hipStream_t st) {
+    if (!on) return hipSuccess;
+    if (!ev[k]) {
+      const hipError_t e = hipEventCreate(&ev[k]);
+      if (e != hipSuccess) return e;
+    }
+    return hipEventRecord(ev[k], st);
+  }
+  hipError_t span(int a, int b, int into) {  // (both events done: the caller has waited for the stream)
+    if (!on) return hipSuccess;
+    float ms = 0;
+    const hipError_t e = hipEventElapsedTime(&ms, ev[a], ev[b]);
+    if (e == hipSuccess) acc[into] += (double)ms * 1e6;
+    return e;
+  }
+  void finish() {
+    if (on)
+      for (int k = 0; k < 4; ++k) ns[k] = (long)acc[k];
+  }
+  hipError_t finish4() {  // the two encodes' stages: events 0-1, 2-3, 3-4, 4-5
+    const int pair[4][2] = {{0, 1}, {2, 3}, {3, 4}, {4, 5}};
+    for (int k = 0; k < 4; ++k)
+      if (const hipError_t e = span(pair[k][0], pair[k][1], k)) return e;
+    finish();
+    return hipSuccess;
+  }
+  ~StageTimer() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 struct lsmck_ctx {
   int dev = 0;
   int ncu = 0;
+  lsmck_host::Options opt;  // lsmck_ctx_set_option's (under mu)
   hipStream_t stream0 = nullptr;
-  uint32_t* d_master = nullptr;  // 4 x 256 slicing tables
-  uint32_t* d_kseg = nullptr;    // 65536
-  uint32_t* d_khi = nullptr;     // 65536
-  uint32_t* d_tinit = nullptr;   // 129
-  uint32_t* d_zero = nullptr;    // 256 zero bytes
+  DevBuf<uint32_t> d_master;  // 4 x 256 slicing tables
+  DevBuf<uint32_t> d_kseg;    // 65536
+  DevBuf<uint32_t> d_khi;     // 65536
+  DevBuf<uint32_t> d_tinit;   // 129
+  DevBuf<uint32_t> d_zero;    // 256 zero bytes
   std::mutex mu;
-  DescScratch scratch;           // device-mode descriptor scratch
+  DescScratch scratch;  // device-mode descriptor scratch
   hipEvent_t scratch_ev = nullptr;
-  unsigned long long* d_verify = nullptr;  // [n_bad, first_bad]; [2..3] the WAL encode's, [4..7] the SSTable encode's words
-  unsigned long long* h_verify = nullptr;  // pinned
-  // device verify / device WAL replay (grow-only; part of the scratch, ordered by scratch_ev)
-  uint32_t* d_vcrc = nullptr;  // computed CRCs
-  size_t cap_vcrc = 0;
-  uint64_t* d_woff = nullptr;  // WAL payload descriptors and stored CRCs
-  size_t cap_woff = 0;
-  uint32_t* d_wlen = nullptr;
-  size_t cap_wlen = 0;
-  uint32_t* d_wexp = nullptr;
-  size_t cap_wexp = 0;
+  DevBuf<unsigned long long> d_verify;  // [n_bad, first_bad]; [2..3] the WAL encode's, [4..7] the SSTable encode's words
+  PinBuf<unsigned long long> h_verify;
+  // device verify / device WAL replay (part of the scratch, ordered by scratch_ev)
+  DevBuf<uint32_t> d_vcrc;  // computed CRCs
+  DevBuf<uint64_t> d_woff;  // WAL payload descriptors and stored CRCs
+  DevBuf<uint32_t> d_wlen;
+  DevBuf<uint32_t> d_wexp;
   // device WAL walk (lsmck_wal.hip): candidate bitmap, ranks, successor levels, chain
   struct {
-    uint64_t* bits = nullptr;
-    size_t cap_bits = 0;
-    uint32_t* pre = nullptr;
-    size_t cap_pre = 0;
-    uint32_t* bsum = nullptr;
-    size_t cap_bsum = 0;
-    uint64_t* pos = nullptr;
-    size_t cap_pos = 0;
-    uint32_t* J = nullptr;
-    size_t cap_J = 0;
-    uint64_t* badpos = nullptr;
-    size_t cap_badpos = 0;
-    uint32_t* chain = nullptr;
-    size_t cap_chain = 0;
-    lsmck_wal_rec* recs = nullptr;
-    size_t cap_recs = 0;
-    lsmck::seg::Compact16* recs16 = nullptr;  // the records in the compact layout (lsmck_wal_replay_verify16)
-    size_t cap_recs16 = 0;
-    unsigned long long* info = nullptr;  // [records, terminal, bad position, candidates (u32 at info+3)]
-    unsigned long long* h_info = nullptr;  // pinned
+    DevBuf<uint64_t> bits;
+    DevBuf<uint32_t> pre;
+    DevBuf<uint32_t> bsum;
+    DevBuf<uint64_t> pos;
+    DevBuf<uint32_t> J;
+    DevBuf<uint64_t> badpos;
+    DevBuf<uint32_t> chain;
+    DevBuf<lsmck_wal_rec> recs;
+    DevBuf<lsmck::seg::Compact16> recs16;  // the records in the compact layout (lsmck_wal_replay_verify16)
+    DevBuf<unsigned long long> info;  // [records, terminal, bad position, candidates (u32 at info+3)]
+    PinBuf<unsigned long long> h_info;
     // the segment walk (lsmck_segwalk.h): per segment guess, exit, outcome,
     // records, placement scan; its round outcome (info words, and pinned)
-    uint64_t* sg = nullptr;
-    uint64_t* sx = nullptr;
-    uint64_t* spre = nullptr;
-    uint32_t* scode = nullptr;
-    uint32_t* srecs = nullptr;
-    size_t cap_seg = 0;
-    uint64_t* sbsum = nullptr;
-    size_t cap_sbsum = 0;
-    unsigned long long* sinfo = nullptr;
-    unsigned long long* h_sinfo = nullptr;
-    uint64_t* scpp = nullptr;  // the emit's checkpoints (segments of 128 KiB and more)
-    uint32_t* scpc = nullptr;
-    size_t cap_cp = 0;
-    lsmck::seg::StageRec* sst = nullptr;  // walk-time staged records (K * scap)
-    size_t cap_sst = 0;
-    uint64_t* sg0 = nullptr;  // the parallel repair's snapshot of sg / sx / scode
-    uint64_t* sx0 = nullptr;
-    uint32_t* scode0 = nullptr;
-    size_t cap_seg0 = 0;
+    DevBuf<uint64_t> sg, sx, spre;
+    DevBuf<uint32_t> scode, srecs;
+    DevBuf<uint64_t> sbsum;
+    DevBuf<unsigned long long> sinfo;
+    PinBuf<unsigned long long> h_sinfo;
+    DevBuf<uint64_t> scpp;  // the emit's checkpoints (segments of 128 KiB and more)
+    DevBuf<uint32_t> scpc;
+    DevBuf<lsmck::seg::StageRec> sst;  // walk-time staged records (K * scap)
+    DevBuf<uint64_t> sg0, sx0;  // the parallel repair's snapshot of sg / sx / scode
+    DevBuf<uint32_t> scode0;
   } wd;
-  // batch WAL encode (lsmck_wal_encode_batch; grow-only, under mu): the
-  // record offsets (n + 1) and the scan's block sums; host form: the uploaded
-  // arenas and commands, and the image
+  // The batch builders (lsmck_wal_encode_batch, lsmck_sstable_encode_batch,
+  // lsmck_memtable_build; all under mu, so never beside each other) share the
+  // device copies of a host-form call's inputs: the key arena, the value
+  // arena and the commands (stage_inputs)
   struct {
-    uint64_t* off = nullptr;
-    size_t cap_off = 0;
-    uint64_t* bsum = nullptr;
-    size_t cap_bsum = 0;
-    uint8_t* keys = nullptr;
-    size_t cap_keys = 0;
-    uint8_t* vals = nullptr;
-    size_t cap_vals = 0;
-    lsmck_wal_cmd* cmds = nullptr;
-    size_t cap_cmds = 0;
-    uint8_t* img = nullptr;
-    size_t cap_img = 0;
+    DevBuf<uint8_t> keys, vals;
+    DevBuf<lsmck_wal_cmd> cmds;
+  } in;
+  // batch WAL encode: the record offsets (n + 1) and the scan's block sums;
+  // host form: the image
+  struct {
+    DevBuf<uint64_t> off, bsum;
+    DevBuf<uint8_t> img;
   } enc;
-  bool enc_time = false;        // option "wal_encode_time": the encode's stages between device events
-  long enc_ns[4] = {0, 0, 0, 0};  // the last timed encode: scan, gather, CRC pass (descriptors included), stamp
-  hipEvent_t enc_ev[6] = {};    // (created by the first timed encode)
-  // batch SSTable encode (lsmck_sstable_encode_batch; grow-only, under mu):
-  // the record offsets (n + 1), the scans' block sums, the first-of-table
-  // flags (n), table_first and the index plan (item bases per table, the
-  // items' table and entry, their offsets), the spans and the digests'
-  // descriptors per table; host form: the uploaded arenas and entries, both
-  // images and the digests
+  StageTimer enc_timer;  // "wal_encode_time": scan, gather, CRC pass (descriptors included), stamp
+  // batch SSTable encode: the record offsets (n + 1), the scans' block sums,
+  // the first-of-table flags (n), table_first and the index plan (item bases
+  // per table, the items' table and entry, their offsets), the spans and the
+  // digests' descriptors per table; host form: both images and the digests
   struct {
-    uint64_t* off = nullptr;
-    size_t cap_off = 0;
-    uint64_t* bsum = nullptr;
-    size_t cap_bsum = 0;
-    uint8_t* first = nullptr;
-    size_t cap_first = 0;
-    uint64_t* tf = nullptr;
-    size_t cap_tf = 0;
-    uint64_t* ibase = nullptr;
-    size_t cap_ibase = 0;
-    uint32_t* item_tab = nullptr;
-    size_t cap_item_tab = 0;
-    uint32_t* item_ent = nullptr;
-    size_t cap_item_ent = 0;
-    uint64_t* ioff = nullptr;
-    size_t cap_ioff = 0;
-    lsmck_sstable_span* spans = nullptr;
-    size_t cap_spans = 0;
-    uint64_t* doff = nullptr;
-    size_t cap_doff = 0;
-    uint32_t* dlen = nullptr;
-    size_t cap_dlen = 0;
-    uint64_t* xoff = nullptr;
-    size_t cap_xoff = 0;
-    uint32_t* xlen = nullptr;
-    size_t cap_xlen = 0;
-    uint8_t* keys = nullptr;
-    size_t cap_keys = 0;
-    uint8_t* vals = nullptr;
-    size_t cap_vals = 0;
-    lsmck_wal_cmd* ents = nullptr;
-    size_t cap_ents = 0;
-    uint8_t* data = nullptr;
-    size_t cap_data = 0;
-    uint8_t* index = nullptr;
-    size_t cap_index = 0;
-    uint8_t* sha = nullptr;  // both digest arrays: 64 bytes per table
-    size_t cap_sha = 0;
+    DevBuf<uint64_t> off, bsum;
+    DevBuf<uint8_t> first;
+    DevBuf<uint64_t> tf, ibase;
+    DevBuf<uint32_t> item_tab, item_ent;
+    DevBuf<uint64_t> ioff;
+    DevBuf<lsmck_sstable_span> spans;
+    DevBuf<uint64_t> doff;
+    DevBuf<uint32_t> dlen;
+    DevBuf<uint64_t> xoff;
+    DevBuf<uint32_t> xlen;
+    DevBuf<uint8_t> data, index;
+    DevBuf<uint8_t> sha;  // both digest arrays: 64 bytes per table
   } sst;  // (its four info words: d_verify[4..7], read back into h_verify[4..7])
-  bool sst_time = false;           // option "sst_encode_time": the encode's stages between device events
-  long sst_ns[4] = {0, 0, 0, 0};   // the last timed encode: scan / order / plan, gather, index writer, digests
-  hipEvent_t sst_ev[6] = {};       // (created by the first timed encode)
-  // batch memtable build (lsmck_memtable_build; grow-only, under mu): the
-  // workspace lsmk_mem_carve cuts into arrays, rocPRIM's temporary storage,
-  // the call's four words (the first invalid command, the round's active
-  // count, mem_bytes, the live entries) and their pinned copy; host form: the
-  // uploaded arenas and commands, the entries and their sources
+  StageTimer sst_timer;  // "sst_encode_time": scan / order / plan, gather, index writer, digests
+  // batch memtable build: the workspace lsmk_mem_carve cuts into arrays,
+  // rocPRIM's temporary storage, the call's four words (the first invalid
+  // command, the round's active count, mem_bytes, the live entries) and their
+  // pinned copy; host form: the entries and their sources
   struct {
-    uint8_t* ws = nullptr;
-    size_t cap_ws = 0;
-    uint8_t* tmp = nullptr;
-    size_t cap_tmp = 0;
-    unsigned long long* info = nullptr;
-    size_t cap_info = 0;
-    unsigned long long* h_info = nullptr;  // pinned
-    uint8_t* keys = nullptr;  // (the key arena alone: no kernel reads a value)
-    size_t cap_keys = 0;
-    lsmck_wal_cmd* cmds = nullptr;
-    size_t cap_cmds = 0;
-    lsmck_wal_cmd* ents = nullptr;
-    size_t cap_ents = 0;
-    uint32_t* src = nullptr;
-    size_t cap_src = 0;
+    DevBuf<uint8_t> ws, tmp;
+    DevBuf<unsigned long long> info;
+    PinBuf<unsigned long long> h_info;
+    DevBuf<lsmck_wal_cmd> ents;
+    DevBuf<uint32_t> src;
   } mem;
-  bool mem_time = false;           // option "mem_build_time": the build's stages between device events
-  long mem_ns[4] = {0, 0, 0, 0};   // the last timed build: validate, mem_chunk, the rounds' fixed-width part, resolve / emit
-  long mem_rounds = 0;             // the last build's rounds
-  hipEvent_t mem_ev[7] = {};       // (created by the first timed build)
+  StageTimer mem_timer;  // "mem_build_time": validate, mem_chunk, the rounds' fixed-width part, resolve / emit
+  long mem_rounds = 0;   // the last build's rounds
   bool wal_recs_direct = false;  // this replay's records go by DMA into the caller's pinned array (under wal_mu)
   bool wal_compact = false;      // this replay's records are lsmck_wal_rec16 (under wal_mu)
   // LSMCK_RECS_DEVICE (under wal_mu): the caller's device array and its capacity
@@ -509,21 +430,9 @@ struct lsmck_ctx {
   void* wal_recs_dev = nullptr;  // lsmck_wal_rec[] or, wal_compact, lsmck_wal_rec16[]
   size_t wal_recs_dev_cap = 0;
   bool wal_recs_dev_emitted = false;
-  int wal_seg = 1;           // device WAL walk: 1 = the segment walk first (default), 0 = candidate doubling only
-  uint64_t wal_seg_bytes = 0;  // segment walk: bytes per segment (0 = auto, ~2^16 segments)
-  bool wal_seg_pack = true;  // segment walk: packed CRC spans (seg::Pack) for the CRC pass
-  long wal_seg_stage = 1;    // segment walk: staged records (seg::StageRec): 0 off, 1 auto slots, else slots per segment
-  int wal_seg_rounds = 16;   // segment walk: repairs before it declines to the candidate-doubling walk
-  int wal_seg_prepair = 2;   // segment walk: parallel repair rounds before the serial repairs (0 = none)
   // The pipelined device replay (wal_replay_pipelined): the log walked in
-  // wal_pipe parts, each part's CRC pass on a CU-masked stream beside the next
-  // part's walk on the CUs left over (0 = off: the walk, then one CRC pass)
-  int wal_pipe = 0;
-  int wal_pipe_first = 4;   // the first part, in 64ths of the log (walked on every CU, nothing beside it)
-  int wal_pipe_cus = 32;    // CUs the walk keeps; the CRC passes take the rest
-  int wal_pipe_layout = 0;  // which CUs the walk keeps: 0 the last wal_pipe_cus, 1 spread (every ncu/cus-th)
-  size_t wal_pipe_min = (size_t)1 << 30;  // logs from this size take the pipeline (when wal_pipe is on)
-  uint64_t wal_pipe_seg = 0;  // the walk parts' segment bytes (0: sized to the walk CUs' resident lanes)
+  // "wal_pipe" parts, each part's CRC pass on a CU-masked stream beside the next
+  // part's walk on the CUs left over
   uint64_t wal_seg_auto = 0;  // (set by the pipeline) the segment bytes of an auto-sized walk, 0: lsmk_wal_seg_bytes
   hipStream_t wal_pw = nullptr;  // the walk's CU-masked stream
   hipStream_t wal_pc = nullptr;  // the CRC passes' CU-masked stream
@@ -533,84 +442,42 @@ struct lsmck_ctx {
   // arrays, so nothing beside it still reads the old ones
   std::function<int()> wal_grow_hook;
   std::atomic<int> last_pipe_parts{0};  // the last device replay's parts (0: not pipelined)
-  int numa_node = -1;    // the device's NUMA node (sysfs), -1 unknown
-  int stage_numa = -2;   // option "stage_numa": -2 the device's node on a multi-node host, -1 off, >= 0 that node
-  int pin_node = -1;     // in effect: pinned buffers and copy threads on this node (-1: none)
+  int numa_node = -1;  // the device's NUMA node (sysfs), -1 unknown
+  int pin_node = -1;   // in effect ("stage_numa"): pinned buffers and copy threads on this node (-1: none)
   // what the last device-walked replay did (lsmck_ctx_get_stat "wal_walk_path" / "wal_seg_repairs" / "wal_segments")
   // (atomic: lsmck_ctx_get_stat reads them under ctx->mu while a replay runs under wal_mu)
   std::atomic<int> last_walk_path{0};
   std::atomic<int> last_seg_repairs{0};
   std::atomic<uint64_t> last_segments{0};
   std::atomic<int> last_seg_prepairs{0};
-  uint8_t* h_wrecs = nullptr;  // device WAL replay: the records' pinned landing buffer (bytes; grow-only)
-  size_t cap_hwrecs = 0;
+  PinBuf<uint8_t> h_wrecs;  // device WAL replay: the records' pinned landing buffer (bytes)
   // the records' read-back on the SDMA engines (lsmck_dma.h): created on first
   // use; "wal_dma_engines" engines (0: hipMemcpyAsync on the staging stream,
   // the round-4 path), the copy cut in "wal_dma_chunks" pieces
   lsmck_dma::Copier* dma = nullptr;
   bool dma_tried = false;
   std::atomic<int> last_recs_dma{0};  // the last read-back: SDMA engines used (0: hipMemcpyAsync)
-  int wal_dma_engines = 4;
-  int wal_dma_chunks = 32;
   hipEvent_t wal_emit_ev = nullptr;  // the emit's end: the records' read-back beside the CRC pass waits for it
-  uint8_t* h_wrecs1 = nullptr;  // split host-image replay: the first part's records (pinned bytes, grow-only)
-  size_t cap_hwrecs1 = 0;
-  hipStream_t wal_rs = nullptr;       // ... read back on their own stream while the second part uploads
+  PinBuf<uint8_t> h_wrecs1;  // split host-image replay: the first part's records (pinned bytes)
+  hipStream_t wal_rs = nullptr;  // ... read back on their own stream while the second part uploads
   hipEvent_t wal_emit1_ev = nullptr;
   std::unique_ptr<lsmck_host::HostPool> pool;  // staging copy threads (created on first use)
-  uint64_t* h_woff = nullptr;  // pinned staging of the same
-  size_t cap_hwoff = 0;
-  uint32_t* h_wlen = nullptr;
-  size_t cap_hwlen = 0;
-  uint32_t* h_wexp = nullptr;
-  size_t cap_hwexp = 0;
-  // the host-batch pipelines alternate over slots 0 and 1; the whole-tree
-  // verify cycles through the first tree_stages of them
-  Stage stage[3];  // host batches and the WAL upload alternate 0 and 1 (kHostSlots); the tree verify uses all 3
-  uint32_t tree_stages = 3;
-  unsigned tree_json_threads = 0;  // whole-tree verify: checksum-file reader threads (0 = 2, 4 from 16k tables)
-  size_t tree_list_batch = 0;  // lsmck_tree_verify: metadata names per listing batch (0 = 1024)
-  long tree_overlap = 2048;  // lsmck_tree_verify: the top level's tables verified while the lower levels are
-                             // listed, when it holds at least this many (0 = never)
-  int variant = 0;  // A/B and diagnostic bits (crc_ablate, crc_stream, sha_order); 0 = default
-  uint32_t tree_active = 0;  // whole-tree verify: files in flight (0 = kTreeActive)
-  uint32_t tree_slice = 0;   // whole-tree verify: bytes of a file per round (0 = kTreeSlice)
-  long tree_open = -1;       // whole-tree verify: files kept open between slices (-1 = RLIMIT_NOFILE budget)
-  uint64_t tree_cpu_file = 0;  // whole-tree verify: files of at least this many bytes go to host threads (0 = 16 MiB)
-  int sha_bucket_shift = 2;  // SHA order key: 2^shift-block buckets for from..1023 blocks (0 = exact; A/B: DESIGN.md 3.2)
-  int sha_bucket_from = 128;
-  int sha_pair = 1;  // SHA-256 batches: two blocks per load window (A/B: DESIGN.md 3.2)
-  int sha_short_blocks = 12;  // SHA-256 ordered batches: messages of at most this many blocks on the lean kernel (0 = off)
-  unsigned tree_list_threads = 0;  // lsmck_tree_verify: metadata parsing threads (0 = kListThreads)
-  unsigned tree_readers = 16;      // whole-tree verify: threads reading a round's slices into its pinned slot
-  size_t wal_prefetch = 4096;  // lsmck_wal_replay_verify: host walk's prefetch distance in bytes (0 = off)
-  uint8_t* wal_host = nullptr;  // lsmck_wal_replay_verify of a device image: pinned host copy (grow-only)
-  size_t wal_host_cap = 0;
+  PinBuf<uint64_t> h_woff;  // pinned staging of d_woff / d_wlen / d_wexp (the host walk's descriptors)
+  PinBuf<uint32_t> h_wlen;
+  PinBuf<uint32_t> h_wexp;
+  // the host-batch pipelines alternate over slots 0 and 1 (kHostSlots), and so
+  // does the WAL upload; the whole-tree verify cycles through the first
+  // "tree_stages" of all three
+  Stage stage[3];
+  PinBuf<uint8_t> wal_host;  // lsmck_wal_replay_verify of a device image: pinned host copy
   std::mutex wal_mu;  // guards wal_host for the duration of one device-image replay
-  size_t wal_chunk = 32u << 20;
-  int wal_gpu_walk = 1;  // lsmck_wal_replay_verify of a device image: header walk on the GPU (0 = copy back, host walk)
   // the GPU walk's scratch budget: this many bytes per log byte + 256 MiB (and
   // at most half the free device memory); over it the log takes the host walk
   size_t wal_walk_budget_per_byte = 8;
-  int wal_register = 0;  // host WAL images: hipHostRegister the caller's pages instead of the staging copy (A/B)
-  size_t wal_part_bytes = 0;  // GPU WAL walk: bytes per part (0 = the whole log, parts only when it does not fit)
-  int wal_split = 1;     // host WAL images of two upload chunks or more: walk the first half during the second's upload
-  // host WAL image upload: bytes per staged / DMA'd chunk.  16 MiB: 6.3 ms
-  // for the 0.24 GB wal_diag image against 6.5 at 64 MiB (the first copy and
-  // the last DMA are not overlapped), 10.7 at 4 MiB (per-chunk costs);
-  // profiles/r03/h/wal_diag_r03h.json
-  size_t wal_stage_bytes = 16u << 20;
-  // host images of at least this many bytes are uploaded whole and walked on
-  // the GPU (0 = always the host walk)
-  size_t wal_upload_min = 1u << 20;
-  uint8_t* d_wimg = nullptr;  // the uploaded host image (grow-only), guarded by wal_mu
-  size_t cap_wimg = 0;
-  unsigned stage_threads = 8;  // host batches: threads copying a pageable chunk into its pinned slot (1 = memcpy)  // lsmck_wal_replay_verify, host image: payload bytes per overlapped CRC batch (0 = one batch)
+  DevBuf<uint8_t> d_wimg;  // the uploaded host image, guarded by wal_mu
   struct {
-    uint32_t* state = nullptr;  // 8 u32 per active slot
-    size_t cap_state = 0;
-    unsigned char* digests = nullptr;  // 32 B per file of the call
-    size_t cap_digests = 0;
+    DevBuf<uint32_t> state;          // 8 u32 per active slot
+    DevBuf<unsigned char> digests;   // 32 B per file of the call
     hipEvent_t kernel_done = nullptr;
   } tree;
 };
@@ -645,9 +512,8 @@ struct ScratchOrder {
 
 int ensure_scratch(DescScratch& sc, size_t nblocks) {
   int rc;
-  if ((rc = ensure_dev(&sc.block_sum, &sc.cap_bs, nblocks))) return rc;
-  if (!sc.total) HIPCHK(hipMalloc((void**)&sc.total, 16));
-  return 0;
+  if ((rc = sc.block_sum.ensure(nblocks))) return rc;
+  return sc.total.ensure(2);
 }
 
 void fill_tables(lsmck_ctx* ctx, CrcParams* P) {
@@ -681,7 +547,7 @@ int crc_fixed_device(lsmck_ctx* ctx, const uint8_t* base, size_t stride, uint32_
     P.nrec = cnt;
     P.out = out + r0;
     fill_tables(ctx, &P);
-    int rc = lsmk_launch_crc32_fixed(&P, ctx->ncu, ctx->variant, st);
+    int rc = lsmk_launch_crc32_fixed(&P, ctx->ncu, (int)ctx->opt.variant, st);
     if (rc) return launch_rc(rc, "crc32_fixed kernel");
   }
   return 0;
@@ -710,20 +576,20 @@ int crc_desc_device(lsmck_ctx* ctx, DescScratch& sc, const uint8_t* base, const 
   P.total_segs = sc.total;
   P.out = out;
   fill_tables(ctx, &P);
-  if (!(ctx->variant & kVariantNoStream)) {
+  if (!(ctx->opt.variant & lsmck_host::kVariantNoStream)) {
     // sorted batches, packed or with small gaps: the stream kernel (a
     // caller's batch is checked on the device; when it is not eligible the
     // walking kernel below takes it, else that kernel exits at once)
-    if (!sc.sflag) HIPCHK(hipMalloc((void**)&sc.sflag, 16));
+    if ((rc = sc.sflag.ensure(4))) return rc;
     const int g = ncu > 0 && ncu < ctx->ncu ? ncu : ctx->ncu;
-    if ((rc = ensure_dev(&sc.scuts, &sc.cap_cuts, (size_t)lsmk_stream_slices_max(ctx->ncu) + 1))) return rc;
+    if ((rc = sc.scuts.ensure((size_t)lsmk_stream_slices_max(ctx->ncu) + 1))) return rc;
     P.sflag = sc.sflag;
     P.scuts = sc.scuts;
-    rc = lsmk_launch_crc32_stream(&P, g, ctx->variant, trusted ? 1 : 0, st);
+    rc = lsmk_launch_crc32_stream(&P, g, (int)ctx->opt.variant, trusted ? 1 : 0, st);
     if (rc) return launch_rc(rc, "crc32_stream kernel");
-    if (trusted || (ctx->variant & kVariantStreamOnly)) return 0;
+    if (trusted || (ctx->opt.variant & lsmck_host::kVariantStreamOnly)) return 0;
   }
-  rc = lsmk_launch_crc32_walk(&P, sc.block_sum, ctx->ncu, ctx->variant, st);
+  rc = lsmk_launch_crc32_walk(&P, sc.block_sum, ctx->ncu, (int)ctx->opt.variant, st);
   return rc ? launch_rc(rc, "crc32_walk kernel") : 0;
 }
 
@@ -735,21 +601,21 @@ constexpr size_t kShaSortMin = 2048;
 int sha_device(lsmck_ctx* ctx, DescScratch& sc, const uint8_t* base, const uint64_t* off, const uint32_t* len,
                size_t stride, uint32_t flen, size_t n, uint8_t* out32, hipStream_t st) {
   const uint32_t* order = nullptr;
-  if (len && n >= kShaSortMin && !(ctx->variant & 0x10000)) {  // 0x10000: batch order (A/B)
+  if (len && n >= kShaSortMin && !(ctx->opt.variant & lsmck_host::kVariantBatchOrder)) {
     if (n >= (1ull << 32)) return lsmck_host::set_error(LSMCK_EINVAL, "more than 2^32-1 messages in one batch");
     int rc;
-    if ((rc = ensure_dev(&sc.sha_keys, &sc.cap_keys, n))) return rc;
-    if ((rc = ensure_dev(&sc.sha_order, &sc.cap_order, n))) return rc;
+    if ((rc = sc.sha_keys.ensure(n))) return rc;
+    if ((rc = sc.sha_order.ensure(n))) return rc;
     size_t tmp = 0;
-    rc = lsmk_sha_order(len, n, sc.sha_keys, sc.sha_order, nullptr, &tmp, ctx->sha_bucket_shift, ctx->sha_bucket_from, st);
+    rc = lsmk_sha_order(len, n, sc.sha_keys, sc.sha_order, nullptr, &tmp, (int)ctx->opt.sha_bucket_shift, (int)ctx->opt.sha_bucket_from, st);
     if (rc) return launch_rc(rc, "sha order (size query)");
-    if ((rc = ensure_dev(&sc.sort_tmp, &sc.cap_tmp, std::max<size_t>(tmp, 1)))) return rc;
-    rc = lsmk_sha_order(len, n, sc.sha_keys, sc.sha_order, sc.sort_tmp, &tmp, ctx->sha_bucket_shift, ctx->sha_bucket_from, st);
+    if ((rc = sc.sort_tmp.ensure(std::max<size_t>(tmp, 1)))) return rc;
+    rc = lsmk_sha_order(len, n, sc.sha_keys, sc.sha_order, sc.sort_tmp, &tmp, (int)ctx->opt.sha_bucket_shift, (int)ctx->opt.sha_bucket_from, st);
     if (rc) return launch_rc(rc, "sha order (radix sort)");
     order = sc.sha_order;
-    if (ctx->sha_short_blocks > 0) {
-      if ((rc = ensure_dev(&sc.sha_split, &sc.cap_split, 1))) return rc;
-      rc = lsmk_sha_split(sc.sha_keys, n, (uint32_t)ctx->sha_short_blocks, sc.sha_split, st);
+    if ((int)ctx->opt.sha_short_blocks > 0) {
+      if ((rc = sc.sha_split.ensure(1))) return rc;
+      rc = lsmk_sha_split(sc.sha_keys, n, (uint32_t)(int)ctx->opt.sha_short_blocks, sc.sha_split, st);
       if (rc) return launch_rc(rc, "sha split");
     }
   }
@@ -762,8 +628,8 @@ int sha_device(lsmck_ctx* ctx, DescScratch& sc, const uint8_t* base, const uint6
   P.nmsg = n;
   P.order = order;
   P.out = out32;
-  P.pair = (uint32_t)ctx->sha_pair;
-  P.split = (order && ctx->sha_short_blocks > 0) ? sc.sha_split : nullptr;
+  P.pair = (uint32_t)(int)ctx->opt.sha_pair;
+  P.split = (order && (int)ctx->opt.sha_short_blocks > 0) ? sc.sha_split.get() : nullptr;
   int rc = lsmk_launch_sha256(&P, st);
   return rc ? launch_rc(rc, "sha256 kernel") : 0;
 }
@@ -804,7 +670,7 @@ lsmck_host::HostPool& host_pool(lsmck_ctx* ctx) {
 
 // the context's NUMA placement from its option (ctx->mu held or not yet shared)
 void apply_numa(lsmck_ctx* ctx) {
-  ctx->pin_node = ctx->stage_numa == -2 ? (numa_node_count() > 1 ? ctx->numa_node : -1) : ctx->stage_numa;
+  ctx->pin_node = (int)ctx->opt.stage_numa == -2 ? (numa_node_count() > 1 ? ctx->numa_node : -1) : (int)ctx->opt.stage_numa;
   if (ctx->pool) {
     cpu_set_t set;
     if (ctx->pin_node >= 0 && node_cpus(ctx->pin_node, &set))
@@ -898,15 +764,15 @@ int run_host_job(lsmck_ctx* ctx, const HostJob& J) {
     if ((rc = stage_retire(S, J))) return rc;
     // descriptors (rebased) and payload
     size_t pay_bytes = use_span ? (size_t)(span_hi - span_lo) : (size_t)bytes;
-    if ((rc = ensure_pinned(ctx->pin_node, &S.h_out, &S.cap_h_out, cnt * esz))) return rc;
-    if ((rc = ensure_dev(&S.d_out, &S.cap_d_out, cnt * esz))) return rc;
-    if ((rc = ensure_dev(&S.d_pay, &S.cap_d_pay, pay_bytes + 16))) return rc;
+    if ((rc = S.h_out.ensure(cnt * esz, ctx->pin_node))) return rc;
+    if ((rc = S.d_out.ensure(cnt * esz))) return rc;
+    if ((rc = S.d_pay.ensure(pay_bytes + 16))) return rc;
     const uint8_t* h_src = nullptr;
     if (J.off) {
-      if ((rc = ensure_pinned(ctx->pin_node, &S.h_off, &S.cap_h_off, cnt))) return rc;
-      if ((rc = ensure_pinned(ctx->pin_node, &S.h_len, &S.cap_h_len, cnt))) return rc;
-      if ((rc = ensure_dev(&S.d_off, &S.cap_d_off, cnt))) return rc;
-      if ((rc = ensure_dev(&S.d_len, &S.cap_d_len, cnt))) return rc;
+      if ((rc = S.h_off.ensure(cnt, ctx->pin_node))) return rc;
+      if ((rc = S.h_len.ensure(cnt, ctx->pin_node))) return rc;
+      if ((rc = S.d_off.ensure(cnt))) return rc;
+      if ((rc = S.d_len.ensure(cnt))) return rc;
       uint64_t pos = 0;
       for (size_t i = 0; i < cnt; ++i) {
         uint64_t o = J.off[r + i];
@@ -918,12 +784,12 @@ int run_host_job(lsmck_ctx* ctx, const HostJob& J) {
     if (use_span && J.pinned) {
       h_src = J.base + span_lo;
     } else {
-      if ((rc = ensure_pinned(ctx->pin_node, &S.h_pay, &S.cap_h_pay, pay_bytes + 16))) return rc;
+      if ((rc = S.h_pay.ensure(pay_bytes + 16, ctx->pin_node))) return rc;
       if (use_span) {
-        stage_copy(ctx, S.h_pay, J.base + span_lo, pay_bytes, ctx->stage_threads);
+        stage_copy(ctx, S.h_pay, J.base + span_lo, pay_bytes, (unsigned)ctx->opt.stage_threads);
       } else if (!J.off) {
         // sparse fixed records: record r+i lands at i*flen
-        const unsigned T = pay_bytes >= (8u << 20) ? std::max(1u, ctx->stage_threads) : 1u;
+        const unsigned T = pay_bytes >= (8u << 20) ? std::max(1u, (unsigned)ctx->opt.stage_threads) : 1u;
         auto gather = [&](size_t i0, size_t i1) {
           for (size_t i = i0; i < i1; ++i) memcpy(S.h_pay + i * J.flen, J.base + (r + i) * J.stride, J.flen);
         };
@@ -931,7 +797,7 @@ int run_host_job(lsmck_ctx* ctx, const HostJob& J) {
       } else {
         // gather: record i lands at its packed position S.h_off[i]; large
         // chunks split the records over stage_threads threads
-        const unsigned T = pay_bytes >= (8u << 20) ? std::max(1u, ctx->stage_threads) : 1u;
+        const unsigned T = pay_bytes >= (8u << 20) ? std::max(1u, (unsigned)ctx->opt.stage_threads) : 1u;
         auto gather = [&](size_t i0, size_t i1) {
           for (size_t i = i0; i < i1; ++i) memcpy(S.h_pay + S.h_off[i], J.base + J.off[r + i], J.len[r + i]);
         };
@@ -948,10 +814,10 @@ int run_host_job(lsmck_ctx* ctx, const HostJob& J) {
       if (J.off) {
         // the staged chunk is sorted by construction: its whole span (sorted,
         // not overlapping: `mono`), or the records packed in order
-        rc = crc_desc_device(ctx, S.scratch, S.d_pay, S.d_off, S.d_len, cnt, (uint32_t*)S.d_out, S.s, true);
+        rc = crc_desc_device(ctx, S.scratch, S.d_pay, S.d_off, S.d_len, cnt, (uint32_t*)S.d_out.get(), S.s, true);
       } else {
         // fixed records: the span starts at record r (gathered: packed at stride flen)
-        rc = crc_fixed_device(ctx, S.d_pay, use_span ? J.stride : J.flen, J.flen, cnt, (uint32_t*)S.d_out, S.s);
+        rc = crc_fixed_device(ctx, S.d_pay, use_span ? J.stride : J.flen, J.flen, cnt, (uint32_t*)S.d_out.get(), S.s);
       }
     } else {
       if (J.off)
@@ -988,7 +854,7 @@ int check_ctx(lsmck_ctx* ctx) {
 int device_verify(lsmck_ctx* ctx, const uint8_t* base, const uint64_t* off, const uint32_t* len,
                   const uint32_t* expected, size_t n, hipStream_t st, uint64_t* n_bad, uint64_t* first_bad,
                   bool trusted = false, const std::function<int()>& while_running = {}) {
-  int rc = ensure_dev(&ctx->d_vcrc, &ctx->cap_vcrc, std::max<size_t>(n, 1));
+  int rc = ctx->d_vcrc.ensure(std::max<size_t>(n, 1));
   if (rc) return rc;
   rc = crc_desc_device(ctx, ctx->scratch, base, off, len, n, ctx->d_vcrc, st, trusted);
   if (rc) return rc;
@@ -1066,18 +932,14 @@ lsmck_ctx* lsmck_ctx_create(int device) {
   for (int k = 1; k < 65536; ++k) khi[k] = lsmck_host::gf2_mulmod(khi[k - 1], Y);
   for (int m = 0; m <= 128; ++m) tinit[m] = lsmck_host::gf2_mulmod(lsmck_host::x_pow_8n(m), 0xFFFFFFFFu);
   bool ok = hipStreamCreateWithFlags(&ctx->stream0, hipStreamNonBlocking) == hipSuccess &&
-            hipMalloc((void**)&ctx->d_master, 4096 * 4) == hipSuccess &&
-            hipMalloc((void**)&ctx->d_kseg, 65536 * 4) == hipSuccess &&
-            hipMalloc((void**)&ctx->d_khi, 65536 * 4) == hipSuccess &&
-            hipMalloc((void**)&ctx->d_tinit, 130 * 4) == hipSuccess &&
-            hipMalloc((void**)&ctx->d_zero, 256) == hipSuccess && hipMemset(ctx->d_zero, 0, 256) == hipSuccess &&
+            !ctx->d_master.ensure(4096) && !ctx->d_kseg.ensure(65536) && !ctx->d_khi.ensure(65536) &&
+            !ctx->d_tinit.ensure(130) && !ctx->d_zero.ensure(64) && hipMemset(ctx->d_zero, 0, 256) == hipSuccess &&
             hipMemcpy(ctx->d_master, master.data(), 4096 * 4, hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(ctx->d_kseg, kseg.data(), 65536 * 4, hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(ctx->d_khi, khi.data(), 65536 * 4, hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(ctx->d_tinit, tinit.data(), 130 * 4, hipMemcpyHostToDevice) == hipSuccess &&
             hipEventCreateWithFlags(&ctx->scratch_ev, hipEventDisableTiming) == hipSuccess &&
-            hipHostMalloc((void**)&ctx->h_verify, 64, hipHostMallocDefault) == hipSuccess &&
-            hipMalloc((void**)&ctx->d_verify, 64) == hipSuccess;
+            !ctx->h_verify.ensure(8, -1) && !ctx->d_verify.ensure(8);
   if (!ok) {
     lsmck_host::set_error(LSMCK_ENOMEM, "context allocation failed");
     lsmck_ctx_destroy(ctx);
@@ -1089,292 +951,14 @@ lsmck_ctx* lsmck_ctx_create(int device) {
 int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value) {
   int rc = check_ctx(ctx);
   if (rc) return rc;
-  if (!key) return lsmck_host::set_error(LSMCK_EINVAL, "null key");
-  if (!strcmp(key, "crc_ablate")) {  // diagnostic only (results are garbage): 3 = payload loads only (the
-                                     // bench's loads-only ceiling), 2 = stream kernel without payload loads
-    if (value != 0 && value != 3 && (!lsmk_ab_ablations() || value < 2 || value > 12))
-      return lsmck_host::set_error(LSMCK_EINVAL, lsmk_ab_ablations() ? "crc_ablate must be 0 or 2..12"
-                                                                     : "crc_ablate must be 0 or 3 (2, 4..12: an A/B "
-                                                                       "library built with -DLSMCK_AB_ABLATIONS)");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->variant = (ctx->variant & ~0xF00) | ((int)value << 8);
-    return 0;
-  }
-  if (!strcmp(key, "tree_active_files")) {  // whole-tree verify: files in flight (0 = 8192); tests use few
-    if (value < 0 || value > (1l << 20)) return lsmck_host::set_error(LSMCK_EINVAL, "tree_active_files: 0..2^20");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->tree_active = (uint32_t)value;
-    return 0;
-  }
-  if (!strcmp(key, "tree_slice_bytes")) {  // whole-tree verify: bytes per file per round (0 = 128 KiB)
-    if (value < 0 || value % 64 || value > (1l << 30))
-      return lsmck_host::set_error(LSMCK_EINVAL, "tree_slice_bytes: a multiple of 64, <= 2^30");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->tree_slice = (uint32_t)value;
-    return 0;
-  }
-  if (!strcmp(key, "tree_list_batch")) {  // lsmck_tree_verify: metadata names per listing batch (0 = 1024; tests)
-    if (value < 0 || value > (1l << 20)) return lsmck_host::set_error(LSMCK_EINVAL, "tree_list_batch: 0 .. 2^20");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->tree_list_batch = (size_t)value;
-    return 0;
-  }
-  if (!strcmp(key, "tree_overlap")) {  // lsmck_tree_verify: the top level verified while the others are listed
-    if (value < 0 || value > (1l << 30)) return lsmck_host::set_error(LSMCK_EINVAL, "tree_overlap: 0 .. 2^30");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->tree_overlap = (long)value;
-    return 0;
-  }
-  if (!strcmp(key, "tree_json_threads")) {  // whole-tree verify: threads reading the checksum files (0 = auto)
-    if (value < 0 || value > 64) return lsmck_host::set_error(LSMCK_EINVAL, "tree_json_threads: 0..64");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->tree_json_threads = (unsigned)value;
-    return 0;
-  }
-  if (!strcmp(key, "tree_stages")) {  // whole-tree verify: pinned slots the rounds cycle through (A/B: 2 or 3)
-    if (value < 2 || value > 3) return lsmck_host::set_error(LSMCK_EINVAL, "tree_stages: 2 or 3");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->tree_stages = (uint32_t)value;
-    return 0;
-  }
-  if (!strcmp(key, "tree_open_files")) {  // whole-tree verify: cap on files kept open (-1 = rlimit budget)
-    if (value < -1) return lsmck_host::set_error(LSMCK_EINVAL, "tree_open_files: -1 or >= 0");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->tree_open = value;
-    return 0;
-  }
-  if (!strcmp(key, "tree_cpu_file_bytes")) {  // whole-tree verify: host-thread SHA-256 for files >= this (0 = 16 MiB)
-    if (value < 0) return lsmck_host::set_error(LSMCK_EINVAL, "tree_cpu_file_bytes: >= 0");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->tree_cpu_file = (uint64_t)value;
-    return 0;
-  }
-  if (!strcmp(key, "tree_list_threads")) {  // A/B: metadata parsing threads of lsmck_tree_verify (0 = 8)
-    if (value < 0 || value > 256) return lsmck_host::set_error(LSMCK_EINVAL, "tree_list_threads: 0..256");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->tree_list_threads = (unsigned)value;
-    return 0;
-  }
-  if (!strcmp(key, "tree_readers")) {  // A/B: whole-tree verify's slice reader threads
-    if (value < 1 || value > 64) return lsmck_host::set_error(LSMCK_EINVAL, "tree_readers: 1..64");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->tree_readers = (unsigned)value;
-    return 0;
-  }
-  if (!strcmp(key, "stage_threads")) {  // A/B: threads of the pageable -> pinned staging copy (1 = one memcpy)
-    if (value < 1 || value > 64) return lsmck_host::set_error(LSMCK_EINVAL, "stage_threads: 1..64");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->stage_threads = (unsigned)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_chunk_bytes")) {  // A/B: WAL replay CRC batches overlapped with the walk (0 = one batch after it)
-    if (value < 0) return lsmck_host::set_error(LSMCK_EINVAL, "wal_chunk_bytes: >= 0");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_chunk = (size_t)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_gpu_walk")) {  // A/B: device-image WAL replay, 1 = GPU header walk (default), 0 = host walk
-    if (value != 0 && value != 1) return lsmck_host::set_error(LSMCK_EINVAL, "wal_gpu_walk must be 0 or 1");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_gpu_walk = (int)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_stage_bytes")) {  // A/B: host WAL image upload chunk (a multiple of 64 KiB, 1..64 MiB)
-    if (value < (1 << 20) || value > (long)kChunkBytes || (value & 0xFFFF))
-      return lsmck_host::set_error(LSMCK_EINVAL, "wal_stage_bytes: a multiple of 64 KiB in [1 MiB, 64 MiB]");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_stage_bytes = (size_t)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_part_bytes")) {  // GPU WAL walk in parts of this many bytes (0 = whole; tests / A/B)
-    if (value < 0 || (value && value < (1l << 20)))
-      return lsmck_host::set_error(LSMCK_EINVAL, "wal_part_bytes: 0 or >= 1 MiB");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_part_bytes = (size_t)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_split")) {  // A/B: host WAL image walked in two parts behind its upload (0 = whole)
-    if (value != 0 && value != 1) return lsmck_host::set_error(LSMCK_EINVAL, "wal_split must be 0 or 1");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_split = (int)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_register")) {  // A/B: host WAL image uploaded by DMA from its own pages, pinned in place
-    if (value != 0 && value != 1) return lsmck_host::set_error(LSMCK_EINVAL, "wal_register must be 0 or 1");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_register = (int)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_upload_min")) {  // A/B: host WAL images from this size go to the GPU walk (0 = never)
-    if (value < 0) return lsmck_host::set_error(LSMCK_EINVAL, "wal_upload_min: >= 0");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_upload_min = (size_t)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_seg_walk")) {  // A/B: device WAL walk, 1 = segment walk first (default), 0 = doubling only
-    if (value != 0 && value != 1) return lsmck_host::set_error(LSMCK_EINVAL, "wal_seg_walk must be 0 or 1");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_seg = (int)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_dma_engines")) {  // WAL records to the host: SDMA engines (0 = hipMemcpyAsync; A/B)
-    if (value < 0 || value > 16) return lsmck_host::set_error(LSMCK_EINVAL, "wal_dma_engines: 0..16");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_dma_engines = (int)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_dma_chunks")) {  // WAL records to the host: pieces of the SDMA copy
-    if (value < 1 || value > lsmck_dma::kMaxChunks)
-      return lsmck_host::set_error(LSMCK_EINVAL, "wal_dma_chunks: 1..64");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_dma_chunks = (int)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_seg_bytes")) {  // segment walk: bytes per segment (0 = auto; tests force small segments)
-    if (value < 0 || (value && (value < 64 || value > (1l << 30))))
-      return lsmck_host::set_error(LSMCK_EINVAL, "wal_seg_bytes: 0 or 64..2^30");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_seg_bytes = (uint64_t)value;
-    return 0;
-  }
-  if (!strcmp(key, "stage_numa")) {  // pinned staging and copy threads: -2 auto (device's node), -1 off, >= 0 a node
-    if (value < -2 || value > 1023) return lsmck_host::set_error(LSMCK_EINVAL, "stage_numa: -2..1023");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->stage_numa = (int)value;
-    apply_numa(ctx);
-    return 0;
-  }
-  if (!strcmp(key, "wal_seg_stage")) {  // segment walk: records staged by the walk (1 auto, 0 off, >= 2 slots/segment)
-    if (value < 0 || value > (1l << 24)) return lsmck_host::set_error(LSMCK_EINVAL, "wal_seg_stage: 0..2^24");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_seg_stage = value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_seg_pack")) {  // A/B: the segment walk's packed CRC spans (1, default) or payloads alone (0)
-    if (value != 0 && value != 1) return lsmck_host::set_error(LSMCK_EINVAL, "wal_seg_pack: 0 or 1");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_seg_pack = value != 0;
-    return 0;
-  }
-  if (!strcmp(key, "wal_seg_prepair")) {  // segment walk: parallel repair rounds before serial repairs (0 = none)
-    if (value < 0 || value > 64) return lsmck_host::set_error(LSMCK_EINVAL, "wal_seg_prepair: 0..64");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_seg_prepair = (int)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_seg_rounds")) {  // segment walk: repair rounds before declining (0 = decline on any failure)
-    if (value < 0 || value > 1024) return lsmck_host::set_error(LSMCK_EINVAL, "wal_seg_rounds: 0..1024");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_seg_rounds = (int)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_pipe")) {  // device WAL replay: parts walked beside the CRC passes (0 = off)
-    if (value < 0 || value > 64) return lsmck_host::set_error(LSMCK_EINVAL, "wal_pipe: 0..64");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_pipe = (int)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_pipe_first")) {  // the pipeline's first part, in 64ths of the log
-    if (value < 1 || value > 63) return lsmck_host::set_error(LSMCK_EINVAL, "wal_pipe_first: 1..63");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_pipe_first = (int)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_pipe_cus")) {  // the pipeline's walk CUs (the CRC passes take the rest)
-    if (value < 1 || value >= ctx->ncu) return lsmck_host::set_error(LSMCK_EINVAL, "wal_pipe_cus: 1..ncu-1");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_pipe_cus = (int)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_pipe_min")) {  // the pipeline's smallest log (tests: small logs through every part)
-    if (value < 0) return lsmck_host::set_error(LSMCK_EINVAL, "wal_pipe_min: >= 0");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_pipe_min = (size_t)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_pipe_seg")) {  // the pipeline walk parts' segment bytes (0 = sized to the walk's CUs)
-    if (value < 0 || (value && (value < 4096 || value > (1l << 30))))
-      return lsmck_host::set_error(LSMCK_EINVAL, "wal_pipe_seg: 0 or 4096..2^30");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_pipe_seg = (uint64_t)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_pipe_layout")) {  // which CUs the walk keeps: 0 the last ones, 1 spread
-    if (value != 0 && value != 1) return lsmck_host::set_error(LSMCK_EINVAL, "wal_pipe_layout: 0 or 1");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_pipe_layout = (int)value;
-    return 0;
-  }
-  if (!strcmp(key, "wal_prefetch")) {  // A/B: bytes the WAL header walk prefetches ahead (0 = off)
-    if (value < 0 || value > (1l << 24)) return lsmck_host::set_error(LSMCK_EINVAL, "wal_prefetch: 0..16 MiB");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->wal_prefetch = (size_t)value;
-    return 0;
-  }
-  if (!strcmp(key, "sha_bucket_from")) {  // A/B: first block count of the coarse SHA buckets
-    if (value < 2 || value > 1024) return lsmck_host::set_error(LSMCK_EINVAL, "sha_bucket_from: 2..1024");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->sha_bucket_from = (int)value;
-    return 0;
-  }
-  if (!strcmp(key, "sha_bucket_shift")) {  // A/B: coarser SHA length buckets (0 = exact block counts)
-    if (value < 0 || value > 6) return lsmck_host::set_error(LSMCK_EINVAL, "sha_bucket_shift: 0..6");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->sha_bucket_shift = (int)value;
-    return 0;
-  }
-  if (!strcmp(key, "sha_short_blocks")) {  // A/B: the lean kernel takes an ordered batch's messages of <= N blocks
-    if (value < 0 || value > 127) return lsmck_host::set_error(LSMCK_EINVAL, "sha_short_blocks: 0..127");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->sha_short_blocks = (int)value;
-    return 0;
-  }
-
-
-
-  if (!strcmp(key, "sha_pair")) {  // A/B: SHA-256 batch kernel loads two blocks (a 128-B line) per window
-    // 2: diagnostic, the pair kernel's main loop without payload loads (digests invalid);
-    // 3: line-aligned loads realigned through LDS rows
-    if (value < 0 || value > 3) return lsmck_host::set_error(LSMCK_EINVAL, "sha_pair must be 0..3");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->sha_pair = (int)value;
-    return 0;
-  }
-  if (!strcmp(key, "sha_order")) {  // A/B: 1 = variable-length SHA batches in decreasing length order (default)
-    if (value != 0 && value != 1) return lsmck_host::set_error(LSMCK_EINVAL, "sha_order must be 0 or 1");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->variant = (ctx->variant & ~0x10000) | (value ? 0 : 0x10000);
-    return 0;
-  }
-  if (!strcmp(key, "crc_stream")) {  // A/B: descriptor batches, 1 = stream kernel for sorted batches (default),
-                                     // 0 = walking kernel only, 2 = stream kernel only (diagnostic: a declined
-                                     // caller batch gets no CRCs)
-    if (value < 0 || value > 2) return lsmck_host::set_error(LSMCK_EINVAL, "crc_stream must be 0, 1 or 2");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->variant = (ctx->variant & ~(kVariantNoStream | kVariantStreamOnly)) |
-                   (value == 0 ? kVariantNoStream : value == 2 ? kVariantStreamOnly : 0);
-    return 0;
-  }
-  if (!strcmp(key, "wal_encode_time")) {  // diagnostic: lsmck_wal_encode_batch's stages between device events
-    if (value != 0 && value != 1) return lsmck_host::set_error(LSMCK_EINVAL, "wal_encode_time must be 0 or 1");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->enc_time = value != 0;
-    return 0;
-  }
-  if (!strcmp(key, "sst_encode_time")) {  // diagnostic: lsmck_sstable_encode_batch's stages between device events
-    if (value != 0 && value != 1) return lsmck_host::set_error(LSMCK_EINVAL, "sst_encode_time must be 0 or 1");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->sst_time = value != 0;
-    return 0;
-  }
-  if (!strcmp(key, "mem_build_time")) {  // diagnostic: lsmck_memtable_build's stages between device events
-    if (value != 0 && value != 1) return lsmck_host::set_error(LSMCK_EINVAL, "mem_build_time must be 0 or 1");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ctx->mem_time = value != 0;
-    return 0;
-  }
-  return lsmck_host::set_error(LSMCK_EINVAL, "unknown option");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  std::string why;
+  if ((rc = lsmck_host::option_set(ctx->opt, key, value, {ctx->ncu, lsmk_ab_ablations() != 0}, &why)))
+    return lsmck_host::set_error(rc, why.c_str());
+  if (!strcmp(key, "stage_numa")) apply_numa(ctx);
+  return 0;
 }
+
 
 int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value) {
   int rc = check_ctx(ctx);
@@ -1400,33 +984,33 @@ int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value) {
   } else if (!strcmp(key, "wal_encode_tile")) {  // lsmck_wal_encode_batch: image bytes per workgroup of the gather
     *value = (long)lsmk_wal_encode_tile();
   } else if (!strcmp(key, "wal_encode_scan_ns")) {  // the last timed encode's stages ("wal_encode_time")
-    *value = ctx->enc_ns[0];
+    *value = ctx->enc_timer.ns[0];
   } else if (!strcmp(key, "wal_encode_gather_ns")) {
-    *value = ctx->enc_ns[1];
+    *value = ctx->enc_timer.ns[1];
   } else if (!strcmp(key, "wal_encode_crc_ns")) {
-    *value = ctx->enc_ns[2];
+    *value = ctx->enc_timer.ns[2];
   } else if (!strcmp(key, "wal_encode_stamp_ns")) {
-    *value = ctx->enc_ns[3];
+    *value = ctx->enc_timer.ns[3];
   } else if (!strcmp(key, "sst_encode_tile")) {  // lsmck_sstable_encode_batch: data bytes per workgroup of the gather
     *value = (long)lsmk_sst_tile();
   } else if (!strcmp(key, "sst_encode_scan_ns")) {  // the last timed encode's stages ("sst_encode_time")
-    *value = ctx->sst_ns[0];
+    *value = ctx->sst_timer.ns[0];
   } else if (!strcmp(key, "sst_encode_gather_ns")) {
-    *value = ctx->sst_ns[1];
+    *value = ctx->sst_timer.ns[1];
   } else if (!strcmp(key, "sst_encode_index_ns")) {
-    *value = ctx->sst_ns[2];
+    *value = ctx->sst_timer.ns[2];
   } else if (!strcmp(key, "sst_encode_sha_ns")) {
-    *value = ctx->sst_ns[3];
+    *value = ctx->sst_timer.ns[3];
   } else if (!strcmp(key, "mem_rounds")) {  // the last lsmck_memtable_build's chunk rounds
     *value = ctx->mem_rounds;
   } else if (!strcmp(key, "mem_validate_ns")) {  // the last timed build's stages ("mem_build_time")
-    *value = ctx->mem_ns[0];
+    *value = ctx->mem_timer.ns[0];
   } else if (!strcmp(key, "mem_chunk_ns")) {
-    *value = ctx->mem_ns[1];
+    *value = ctx->mem_timer.ns[1];
   } else if (!strcmp(key, "mem_sort_ns")) {
-    *value = ctx->mem_ns[2];
+    *value = ctx->mem_timer.ns[2];
   } else if (!strcmp(key, "mem_resolve_ns")) {
-    *value = ctx->mem_ns[3];
+    *value = ctx->mem_timer.ns[3];
   } else {
     return lsmck_host::set_error(LSMCK_EINVAL, "unknown stat");
   }
@@ -1437,70 +1021,14 @@ void lsmck_ctx_destroy(lsmck_ctx* ctx) {
   if (!ctx) return;
   DevGuard g(ctx->dev);
   (void)hipDeviceSynchronize();
-  for (auto& S : ctx->stage) S.release();
-  ctx->scratch.release();
-  if (ctx->tree.state) (void)hipFree(ctx->tree.state);
-  if (ctx->tree.digests) (void)hipFree(ctx->tree.digests);
-  if (ctx->tree.kernel_done) (void)hipEventDestroy(ctx->tree.kernel_done);
-  if (ctx->d_master) (void)hipFree(ctx->d_master);
-  if (ctx->d_kseg) (void)hipFree(ctx->d_kseg);
-  if (ctx->d_khi) (void)hipFree(ctx->d_khi);
-  if (ctx->d_tinit) (void)hipFree(ctx->d_tinit);
-  if (ctx->d_zero) (void)hipFree(ctx->d_zero);
-  if (ctx->d_verify) (void)hipFree(ctx->d_verify);
-  for (void* p : {(void*)ctx->wd.bits, (void*)ctx->wd.pre, (void*)ctx->wd.bsum, (void*)ctx->wd.pos, (void*)ctx->wd.J,
-                  (void*)ctx->wd.badpos, (void*)ctx->wd.chain, (void*)ctx->wd.recs, (void*)ctx->wd.info})
-    if (p) (void)hipFree(p);
-  if (ctx->wd.h_info) host_free(ctx->wd.h_info);
-  for (void* p : {(void*)ctx->wd.sg, (void*)ctx->wd.sx, (void*)ctx->wd.spre, (void*)ctx->wd.scode,
-                  (void*)ctx->wd.srecs, (void*)ctx->wd.sbsum, (void*)ctx->wd.sinfo, (void*)ctx->wd.scpp,
-                  (void*)ctx->wd.scpc, (void*)ctx->wd.sst, (void*)ctx->wd.sg0, (void*)ctx->wd.sx0,
-                  (void*)ctx->wd.scode0})
-    if (p) (void)hipFree(p);
-  if (ctx->wd.h_sinfo) host_free(ctx->wd.h_sinfo);
-  for (void* p : {(void*)ctx->d_vcrc, (void*)ctx->d_woff, (void*)ctx->d_wlen, (void*)ctx->d_wexp})
-    if (p) (void)hipFree(p);
-  for (void* p : {(void*)ctx->h_woff, (void*)ctx->h_wlen, (void*)ctx->h_wexp})
-    if (p) host_free(p);
-  for (void* p : {(void*)ctx->enc.off, (void*)ctx->enc.bsum, (void*)ctx->enc.keys, (void*)ctx->enc.vals,
-                  (void*)ctx->enc.cmds, (void*)ctx->enc.img})
-    if (p) (void)hipFree(p);
-  for (hipEvent_t e : ctx->enc_ev)
-    if (e) (void)hipEventDestroy(e);
-  {
-    auto& S = ctx->sst;
-    for (void* p : {(void*)S.off, (void*)S.bsum, (void*)S.first, (void*)S.tf, (void*)S.ibase, (void*)S.item_tab,
-                    (void*)S.item_ent, (void*)S.ioff, (void*)S.spans, (void*)S.doff, (void*)S.dlen, (void*)S.xoff,
-                    (void*)S.xlen, (void*)S.keys, (void*)S.vals, (void*)S.ents, (void*)S.data, (void*)S.index,
-                    (void*)S.sha})
-      if (p) (void)hipFree(p);
-  }
-  for (hipEvent_t e : ctx->sst_ev)
-    if (e) (void)hipEventDestroy(e);
-  {
-    auto& M = ctx->mem;
-    for (void* p : {(void*)M.ws, (void*)M.tmp, (void*)M.info, (void*)M.keys, (void*)M.cmds,
-                    (void*)M.ents, (void*)M.src})
-      if (p) (void)hipFree(p);
-    if (M.h_info) host_free(M.h_info);
-  }
-  for (hipEvent_t e : ctx->mem_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (ctx->h_verify) host_free(ctx->h_verify);
-  if (ctx->h_wrecs) host_free(ctx->h_wrecs);
-  if (ctx->wd.recs16) (void)hipFree(ctx->wd.recs16);
+  // what is not a buffer; the buffers (and the slots' streams and events, the
+  // builders' timers) go with the context below, this device still current
   lsmck_dma::destroy(ctx->dma);
-  if (ctx->wal_emit_ev) (void)hipEventDestroy(ctx->wal_emit_ev);
-  if (ctx->h_wrecs1) host_free(ctx->h_wrecs1);
-  if (ctx->wal_emit1_ev) (void)hipEventDestroy(ctx->wal_emit1_ev);
-  if (ctx->wal_rs) (void)hipStreamDestroy(ctx->wal_rs);
-  if (ctx->wal_pw) (void)hipStreamDestroy(ctx->wal_pw);
-  if (ctx->wal_pc) (void)hipStreamDestroy(ctx->wal_pc);
+  for (hipEvent_t e : {ctx->tree.kernel_done, ctx->wal_emit_ev, ctx->wal_emit1_ev, ctx->scratch_ev})
+    if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->wal_pipe_ev) (void)hipEventDestroy(e);
-  if (ctx->wal_host) host_free(ctx->wal_host);
-  if (ctx->d_wimg) (void)hipFree(ctx->d_wimg);
-  if (ctx->scratch_ev) (void)hipEventDestroy(ctx->scratch_ev);
-  if (ctx->stream0) (void)hipStreamDestroy(ctx->stream0);
+  for (hipStream_t s : {ctx->wal_rs, ctx->wal_pw, ctx->wal_pc, ctx->stream0})
+    if (s) (void)hipStreamDestroy(s);
   delete ctx;
 }
 
@@ -1608,9 +1136,9 @@ static int wal_bitmap_ensure(lsmck_ctx* ctx, size_t n) {
   auto& W = ctx->wd;
   int rc;
   const size_t nw = (size_t)lsmk_wal_words(n), nb = (size_t)lsmk_wal_scan_blocks(n);
-  if ((rc = ensure_dev(&W.bits, &W.cap_bits, std::max<size_t>(nw, 1))) ||
-      (rc = ensure_dev(&W.pre, &W.cap_pre, std::max<size_t>(nw, 1))) ||
-      (rc = ensure_dev(&W.bsum, &W.cap_bsum, nb + 1)))
+  if ((rc = W.bits.ensure(std::max<size_t>(nw, 1))) ||
+      (rc = W.pre.ensure(std::max<size_t>(nw, 1))) ||
+      (rc = W.bsum.ensure(nb + 1)))
     return rc;
   return 0;
 }
@@ -1674,10 +1202,8 @@ static int wal_walk_part(lsmck_ctx* ctx, const uint8_t* img, size_t n, uint64_t 
     out->over = (double)need / (double)std::max<size_t>(budget, 1);
     return kWalTooBig;
   }
-  if (ensure_dev(&W.pos, &W.cap_pos, std::max<size_t>(nc, 1)) ||
-      ensure_dev(&W.J, &W.cap_J, std::max<size_t>((size_t)levels * nc, 1)) ||
-      ensure_dev(&W.badpos, &W.cap_badpos, std::max<size_t>(nc, 1)) ||
-      ensure_dev(&W.chain, &W.cap_chain, (size_t)1 << levels)) {
+  if (W.pos.try_ensure(nc) || W.J.try_ensure((size_t)levels * nc) || W.badpos.try_ensure(nc) ||
+      W.chain.try_ensure((size_t)1 << levels)) {
     (void)hipGetLastError();  // the failed hipMalloc's sticky error
     out->over = 2.0;
     return kWalTooBig;
@@ -1693,17 +1219,17 @@ static int wal_walk_part(lsmck_ctx* ctx, const uint8_t* img, size_t n, uint64_t 
   out->tpos = W.h_info[2];
   if (out->m) {  // records -> lsmck_wal_rec, payload descriptors, stored CRCs (after the first `at`)
     const size_t tot = at + out->m;
-    if ((rc = ensure_dev_keep(&W.recs, &W.cap_recs, tot, at, st)) ||
-        (rc = ensure_dev_keep(&ctx->d_woff, &ctx->cap_woff, tot, at, st)) ||
-        (rc = ensure_dev_keep(&ctx->d_wlen, &ctx->cap_wlen, tot, at, st)) ||
-        (rc = ensure_dev_keep(&ctx->d_wexp, &ctx->cap_wexp, tot, at, st)) ||
-        (rc = ensure_dev_keep(&ctx->d_vcrc, &ctx->cap_vcrc, tot, at, st)))
+    if ((rc = W.recs.ensure_keep(tot, at, st)) ||
+        (rc = ctx->d_woff.ensure_keep(tot, at, st)) ||
+        (rc = ctx->d_wlen.ensure_keep(tot, at, st)) ||
+        (rc = ctx->d_wexp.ensure_keep(tot, at, st)) ||
+        (rc = ctx->d_vcrc.ensure_keep(tot, at, st)))
       return rc;
     rc = lsmk_wal_emit(img, n, W.chain, W.pos, W.info, (uint32_t)out->m, W.recs + at, ctx->d_woff + at,
                        ctx->d_wlen + at, ctx->d_wexp + at, st);
     if (rc) return launch_rc(rc, "wal emit kernel");
     if (ctx->wal_compact) {  // the caller's layout: lsmck_wal_rec16 (the segment walk emits it directly)
-      if ((rc = ensure_dev_keep(&W.recs16, &W.cap_recs16, tot, at, st))) return rc;
+      if ((rc = W.recs16.ensure_keep(tot, at, st))) return rc;
       if ((rc = lsmk_wal_recs_compact(W.recs + at, W.recs16 + at, out->m, st)))
         return launch_rc(rc, "wal record compaction kernel");
     }
@@ -1766,16 +1292,16 @@ static int wal_read_back(lsmck_ctx* ctx, uint8_t* land, const uint8_t* src, size
   HIPCHK(hipEventSynchronize(ctx->wal_emit_ev));
   auto copy_out = [&](size_t a, size_t b) {  // land [a, b) -> out, several threads for large pieces
     const size_t len = b - a;
-    const unsigned T = len >= (4u << 20) ? std::max(1u, std::min(ctx->stage_threads, 8u)) : 1u;
+    const unsigned T = len >= (4u << 20) ? std::max(1u, std::min((unsigned)ctx->opt.stage_threads, 8u)) : 1u;
     host_pool(ctx).run(T, [&](unsigned t) {
       const size_t x = a + (len * t / T & ~(size_t)4095), y = t + 1 == T ? b : a + (len * (t + 1) / T & ~(size_t)4095);
       if (y > x) memcpy(out + x, land + x, y - x);
     });
   };
-  lsmck_dma::Copier* dc = ctx->wal_dma_engines ? dma_copier(ctx) : nullptr;
+  lsmck_dma::Copier* dc = (int)ctx->opt.wal_dma_engines ? dma_copier(ctx) : nullptr;
   lsmck_dma::Job job;
-  if (dc && lsmck_dma::d2h(dc, land, src, bytes, ctx->wal_dma_engines, ctx->wal_dma_chunks, &job) == 0) {
-    const int E = std::max(1, std::min(ctx->wal_dma_engines, lsmck_dma::engines(dc)));
+  if (dc && lsmck_dma::d2h(dc, land, src, bytes, (int)ctx->opt.wal_dma_engines, (int)ctx->opt.wal_dma_chunks, &job) == 0) {
+    const int E = std::max(1, std::min((int)ctx->opt.wal_dma_engines, lsmck_dma::engines(dc)));
     ctx->last_recs_dma = E;
     int werr = 0;
     for (int i = 0; i < job.n;) {  // (a round: the next piece of every engine)
@@ -1819,8 +1345,8 @@ static int wal_finish(lsmck_ctx* ctx, const uint8_t* img, size_t m, uint32_t ter
   ctx->last_recs_dma = 0;
   // the device array that holds records [0, m): the caller's when the emit wrote them there
   const uint8_t* dsrc = ctx->wal_recs_dev && ctx->wal_recs_dev_emitted ? (const uint8_t*)recs
-                        : ctx->wal_compact                             ? (const uint8_t*)W.recs16
-                                                                       : (const uint8_t*)W.recs;
+                        : ctx->wal_compact                             ? (const uint8_t*)W.recs16.get()
+                                                                       : (const uint8_t*)W.recs.get();
   if (m) {
     const size_t ntake = std::min(m, cap) > done ? std::min(m, cap) - done : 0;  // records for the caller's array
     uint8_t* const rb = (uint8_t*)recs;
@@ -1834,7 +1360,7 @@ static int wal_finish(lsmck_ctx* ctx, const uint8_t* img, size_t m, uint32_t ter
       if (ctx->wal_recs_direct) {
         land = rb + done * rsz;  // page-locked (LSMCK_RECS_PINNED): straight in
       } else {
-        if ((rc = ensure_pinned(ctx->pin_node, &ctx->h_wrecs, &ctx->cap_hwrecs, ntake * rsz))) return rc;
+        if ((rc = ctx->h_wrecs.ensure(ntake * rsz, ctx->pin_node))) return rc;
         land = ctx->h_wrecs;
       }
       if (!ctx->wal_emit_ev) HIPCHK(hipEventCreateWithFlags(&ctx->wal_emit_ev, hipEventDisableTiming));
@@ -1894,10 +1420,8 @@ static int wal_finish(lsmck_ctx* ctx, const uint8_t* img, size_t m, uint32_t ter
 static int wal_walk_setup(lsmck_ctx* ctx, size_t n) {
   auto& W = ctx->wd;
   int rc;
-  if ((rc = wal_bitmap_ensure(ctx, n))) return rc;
-  if (!W.info) HIPCHK(hipMalloc((void**)&W.info, 64));
-  if (!W.h_info) HIPCHK(hipHostMalloc((void**)&W.h_info, 64, hipHostMallocDefault));
-  return 0;
+  if ((rc = wal_bitmap_ensure(ctx, n)) || (rc = W.info.ensure(8))) return rc;
+  return W.h_info.ensure(8, -1);
 }
 
 // The walk from position r to the end of the image in parts: each part is a
@@ -1982,7 +1506,7 @@ static int wal_seg_walk(lsmck_ctx* ctx, const uint8_t* img, size_t n, uint64_t s
     return 0;
   }
   if (lim > n || lim <= start) lim = n;
-  uint64_t S = lsmk_wal_seg_bytes(lim - start, ctx->wal_seg_bytes ? ctx->wal_seg_bytes : ctx->wal_seg_auto);
+  uint64_t S = lsmk_wal_seg_bytes(lim - start, (uint64_t)ctx->opt.wal_seg_bytes ? (uint64_t)ctx->opt.wal_seg_bytes : ctx->wal_seg_auto);
   sg::SegArgs a{};
   int resegs = 0, prepairs = 0, repairs = 0;
   ctx->last_seg_prepairs = 0;
@@ -2002,52 +1526,15 @@ static int wal_seg_walk(lsmck_ctx* ctx, const uint8_t* img, size_t n, uint64_t s
         (void)hipGetLastError();
         return kWalSegDecline;
       };
-      if (ensure_dev(&W.sbsum, &W.cap_sbsum, (size_t)lsmk_wal_seg_scan_blocks(K) + 1)) return alloc_fail();
-      if (W.cap_seg < (size_t)K + 1) {
-        for (void* p : {(void*)W.sg, (void*)W.sx, (void*)W.spre, (void*)W.scode, (void*)W.srecs})
-          if (p) (void)hipFree(p);
-        const size_t c = std::max<size_t>((size_t)K + 1, W.cap_seg * 3 / 2);
-        W.sg = W.sx = W.spre = nullptr;
-        W.scode = W.srecs = nullptr;
-        W.cap_seg = 0;
-        if (hipMalloc((void**)&W.sg, c * 8) != hipSuccess || hipMalloc((void**)&W.sx, c * 8) != hipSuccess ||
-            hipMalloc((void**)&W.spre, c * 8) != hipSuccess || hipMalloc((void**)&W.scode, c * 4) != hipSuccess ||
-            hipMalloc((void**)&W.srecs, c * 4) != hipSuccess) {
-          for (void** p : {(void**)&W.sg, (void**)&W.sx, (void**)&W.spre, (void**)&W.scode, (void**)&W.srecs}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-          }
-          return alloc_fail();
-        }
-        W.cap_seg = c;
-      }
-      if (!W.sinfo && hipMalloc((void**)&W.sinfo, sg::kInfoWords * 8) != hipSuccess) {
-        W.sinfo = nullptr;
+      const size_t k1 = (size_t)K + 1;
+      if (W.sbsum.try_ensure((size_t)lsmk_wal_seg_scan_blocks(K) + 1) || W.sg.try_ensure(k1) || W.sx.try_ensure(k1) ||
+          W.spre.try_ensure(k1) || W.scode.try_ensure(k1) || W.srecs.try_ensure(k1) ||
+          W.sinfo.try_ensure(sg::kInfoWords) || W.h_sinfo.try_ensure(sg::kInfoWords, -1))
         return alloc_fail();
-      }
-      if (!W.h_sinfo && hipHostMalloc((void**)&W.h_sinfo, sg::kInfoWords * 8, hipHostMallocDefault) != hipSuccess) {
-        W.h_sinfo = nullptr;
-        return alloc_fail();
-      }
       // the emit from checkpoints every 64 KiB (up to 32 per segment): its
       // walks run 32x as many threads, each a 32nd as long
       const uint32_t nsub = S >= (128u << 10) ? (uint32_t)std::min<uint64_t>(32, S >> 16) : 1u;
-      if (nsub > 1 && W.cap_cp < (size_t)K * nsub) {
-        for (void* p : {(void*)W.scpp, (void*)W.scpc})
-          if (p) (void)hipFree(p);
-        W.scpp = nullptr;
-        W.scpc = nullptr;
-        W.cap_cp = 0;
-        const size_t c = (size_t)K * nsub;
-        if (hipMalloc((void**)&W.scpp, c * 8) != hipSuccess || hipMalloc((void**)&W.scpc, c * 4) != hipSuccess) {
-          if (W.scpp) (void)hipFree(W.scpp);
-          if (W.scpc) (void)hipFree(W.scpc);
-          W.scpp = nullptr;
-          W.scpc = nullptr;
-          return alloc_fail();
-        }
-        W.cap_cp = c;
-      }
+      if (nsub > 1 && (W.scpp.try_ensure((size_t)K * nsub) || W.scpc.try_ensure((size_t)K * nsub))) return alloc_fail();
       // the walk stages each segment's records in scap slots (auto: an
       // eighth of the walked bytes, 64 MiB .. 8 GiB, over the segments, and
       // at most a quarter of the free device memory (less the records'
@@ -2055,27 +1542,27 @@ static int wal_seg_walk(lsmck_ctx* ctx, const uint8_t* img, size_t n, uint64_t s
       // segment with more is emitted by a second walk of its headers, and so
       // is every segment when the slots cannot be had (scap 0)
       uint32_t scap = 0;
-      if (ctx->wal_seg_stage && S <= sg::kStageMaxSeg) {  // (a staged record keeps its offset in 31 bits)
+      if (ctx->opt.wal_seg_stage && S <= sg::kStageMaxSeg) {  // (a staged record keeps its offset in 31 bits)
         const uint64_t most = S / 9 + 1;
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-        const uint64_t have = W.sst ? (uint64_t)W.cap_sst * sizeof(sg::StageRec) : 0;  // (reused, not new)
+        const uint64_t have = (uint64_t)W.sst.cap() * sizeof(sg::StageRec);  // (reused, not new)
         const uint64_t budget = std::min<uint64_t>(
             std::min<uint64_t>(std::max<uint64_t>((lim - start) / 8, 64ull << 20), 8ull << 30),
             (uint64_t)free_b / 4 + have);
-        const uint64_t c = std::min<uint64_t>(most, ctx->wal_seg_stage >= 2 ? (uint64_t)ctx->wal_seg_stage
+        const uint64_t c = std::min<uint64_t>(most, ctx->opt.wal_seg_stage >= 2 ? (uint64_t)ctx->opt.wal_seg_stage
                                                                                : budget / (sizeof(sg::StageRec) * K));
         if (c >= 1) {
           scap = (uint32_t)c;
-          if (ensure_dev(&W.sst, &W.cap_sst, (size_t)K * scap)) {
+          if (W.sst.try_ensure((size_t)K * scap)) {
             (void)hipGetLastError();  // no slots: every segment is emitted by its second walk
             scap = 0;
           }
         }
       }
       a = sg::SegArgs{img, n, start, S, K, W.sg, W.sx, W.scode, W.srecs, W.spre, W.sinfo, lim,
-                      nsub, S / nsub, nsub > 1 ? W.scpp : nullptr, nsub > 1 ? W.scpc : nullptr,
-                      scap ? W.sst : nullptr, scap};
+                      nsub, S / nsub, nsub > 1 ? W.scpp.get() : nullptr, nsub > 1 ? W.scpc.get() : nullptr,
+                      scap ? W.sst.get() : nullptr, scap};
       if ((rc = lsmk_wal_seg_walk(&a, st))) return launch_rc(rc, "wal segment walk kernel");
     }
     if ((rc = lsmk_wal_seg_round(&a, W.sbsum, st))) return launch_rc(rc, "wal segment check kernels");
@@ -2087,22 +1574,12 @@ static int wal_seg_walk(lsmck_ctx* ctx, const uint8_t* img, size_t n, uint64_t s
     // Several failures: a parallel repair round first (seg::seg_prepair:
     // every segment from its predecessor's exit at once -- a log of logs
     // fails at every segment and is whole after one), then check again
-    if (nfail >= 2 && prepairs < ctx->wal_seg_prepair) {
-      if (W.cap_seg0 < W.cap_seg) {
-        for (void** p : {(void**)&W.sg0, (void**)&W.sx0, (void**)&W.scode0}) {
-          if (*p) (void)hipFree(*p);
-          *p = nullptr;
-        }
-        W.cap_seg0 = 0;
-        if (hipMalloc((void**)&W.sg0, W.cap_seg * 8) != hipSuccess ||
-            hipMalloc((void**)&W.sx0, W.cap_seg * 8) != hipSuccess ||
-            hipMalloc((void**)&W.scode0, W.cap_seg * 4) != hipSuccess) {
-          (void)hipGetLastError();  // (no room for the snapshot: the serial repairs below)
-        } else {
-          W.cap_seg0 = W.cap_seg;
-        }
-      }
-      if (W.cap_seg0 >= a.K) {
+    if (nfail >= 2 && prepairs < (int)ctx->opt.wal_seg_prepair) {
+      // (sized like sg, which holds a.K + 1 and more; no room for the snapshot: the serial repairs below)
+      const size_t c0 = W.sg.cap();
+      if (W.sg0.try_ensure(c0) || W.sx0.try_ensure(c0) || W.scode0.try_ensure(c0)) {
+        (void)hipGetLastError();
+      } else {
         if ((rc = lsmk_wal_seg_prepair(&a, W.sg0, W.sx0, W.scode0, st)))
           return launch_rc(rc, "wal segment parallel repair");
         ++prepairs;
@@ -2113,14 +1590,14 @@ static int wal_seg_walk(lsmck_ctx* ctx, const uint8_t* img, size_t n, uint64_t s
     // Many failures still: records longer than the segments (a segment
     // inside one has no true entry, and a bogus start there is taken) --
     // segments 16x longer, once or twice, unless the caller fixed the size
-    if (repairs == 0 && !ctx->wal_seg_bytes && resegs < 2 && nfail > std::max<uint32_t>(64, a.K / 512) &&
+    if (repairs == 0 && !(uint64_t)ctx->opt.wal_seg_bytes && resegs < 2 && nfail > std::max<uint32_t>(64, a.K / 512) &&
         S < (1ull << 30)) {
       S <<= 4;
       ++resegs;
       walk = true;
       continue;
     }
-    if (repairs >= ctx->wal_seg_rounds) {
+    if (repairs >= (int)ctx->opt.wal_seg_rounds) {
       ctx->last_seg_repairs = repairs;
       return kWalSegDecline;
     }
@@ -2142,29 +1619,30 @@ static int wal_seg_walk(lsmck_ctx* ctx, const uint8_t* img, size_t n, uint64_t s
     if (ctx->wal_recs_dev_emitted && at > 0 && !dev) return kWalPipeRestart;
     const bool c16 = ctx->wal_compact;
     if (ctx->wal_grow_hook) {  // (a pipelined replay: the CRC passes and read-backs beside it let go first)
-      const size_t rcap = dev ? tot : c16 ? W.cap_recs16 : W.cap_recs;
-      if ((rcap < tot || ctx->cap_woff < tot || ctx->cap_wlen < tot || ctx->cap_wexp < tot || ctx->cap_vcrc < tot) &&
+      const size_t rcap = dev ? tot : c16 ? W.recs16.cap() : W.recs.cap();
+      if ((rcap < tot || ctx->d_woff.cap() < tot || ctx->d_wlen.cap() < tot || ctx->d_wexp.cap() < tot ||
+           ctx->d_vcrc.cap() < tot) &&
           (rc = ctx->wal_grow_hook()))
         return rc;
     }
-    if ((!dev && !c16 && (rc = ensure_dev_keep(&W.recs, &W.cap_recs, tot, at, st))) ||
-        (!dev && c16 && (rc = ensure_dev_keep(&W.recs16, &W.cap_recs16, tot, at, st))) ||
-        (rc = ensure_dev_keep(&ctx->d_woff, &ctx->cap_woff, tot, at, st)) ||
-        (rc = ensure_dev_keep(&ctx->d_wlen, &ctx->cap_wlen, tot, at, st)) ||
-        (rc = ensure_dev_keep(&ctx->d_wexp, &ctx->cap_wexp, tot, at, st)) ||
-        (rc = ensure_dev_keep(&ctx->d_vcrc, &ctx->cap_vcrc, tot, at, st)))
+    if ((!dev && !c16 && (rc = W.recs.ensure_keep(tot, at, st))) ||
+        (!dev && c16 && (rc = W.recs16.ensure_keep(tot, at, st))) ||
+        (rc = ctx->d_woff.ensure_keep(tot, at, st)) ||
+        (rc = ctx->d_wlen.ensure_keep(tot, at, st)) ||
+        (rc = ctx->d_wexp.ensure_keep(tot, at, st)) ||
+        (rc = ctx->d_vcrc.ensure_keep(tot, at, st)))
       return rc;
     void* to = dev ? ctx->wal_recs_dev : c16 ? (void*)W.recs16 : (void*)W.recs;
-    if (ctx->wal_seg_pack) {
+    if (ctx->opt.wal_seg_pack) {
       rc = lsmk_wal_seg_emit_packed(&a, at, to, c16, ctx->d_woff, ctx->d_wlen, ctx->d_wexp, tot, st);
     } else {
       rc = lsmk_wal_seg_emit(&a, at, to, c16, ctx->d_woff, ctx->d_wlen, ctx->d_wexp, st);
     }
     if (rc) return launch_rc(rc, "wal segment emit kernel");
     if ((rc = lsmk_wal_seg_place(&a, at, to, c16, ctx->d_woff, ctx->d_wlen, ctx->d_wexp, tot,
-                                 ctx->wal_seg_pack ? 1 : 0, st)))
+                                 ctx->opt.wal_seg_pack ? 1 : 0, st)))
       return launch_rc(rc, "wal segment place kernel");
-    out->packed = ctx->wal_seg_pack;
+    out->packed = ctx->opt.wal_seg_pack;
     ctx->wal_recs_dev_emitted = dev;
   }
   if (!ctx->wal_emit_ev) HIPCHK(hipEventCreateWithFlags(&ctx->wal_emit_ev, hipEventDisableTiming));
@@ -2177,8 +1655,8 @@ static int wal_seg_walk(lsmck_ctx* ctx, const uint8_t* img, size_t n, uint64_t s
 // A persistent stream kernel sized to the rest's CU count keeps each of its
 // CUs to itself, so neither side's workgroups wait for the other's.
 static int wal_pipe_streams(lsmck_ctx* ctx) {
-  const int N = ctx->ncu, cus = std::min(ctx->wal_pipe_cus, N - 1);
-  const int key = cus * 2 + ctx->wal_pipe_layout;
+  const int N = ctx->ncu, cus = std::min((int)ctx->opt.wal_pipe_cus, N - 1);
+  const int key = cus * 2 + (int)ctx->opt.wal_pipe_layout;
   if (ctx->wal_pw && ctx->wal_pc && ctx->wal_pipe_key == key) return 0;
   for (hipStream_t* s : {&ctx->wal_pw, &ctx->wal_pc})
     if (*s) {
@@ -2188,7 +1666,7 @@ static int wal_pipe_streams(lsmck_ctx* ctx) {
     }
   std::vector<uint32_t> mw((size_t)(N + 31) / 32, 0u), mc((size_t)(N + 31) / 32, 0u);
   std::vector<char> walk((size_t)N, 0);
-  if (ctx->wal_pipe_layout == 0) {
+  if ((int)ctx->opt.wal_pipe_layout == 0) {
     for (int i = N - cus; i < N; ++i) walk[(size_t)i] = 1;
   } else {
     for (int j = 0; j < cus; ++j) walk[(size_t)(((int64_t)j * N) / cus + N / cus - 1)] = 1;
@@ -2221,8 +1699,8 @@ static int wal_replay_pipelined(lsmck_ctx* ctx, const uint8_t* img, size_t n, vo
   auto& Wd = ctx->wd;
   int rc;
   if ((rc = wal_pipe_streams(ctx))) return rc;
-  const int P = ctx->wal_pipe;
-  const int crc_cus = ctx->ncu - std::min(ctx->wal_pipe_cus, ctx->ncu - 1);
+  const int P = (int)ctx->opt.wal_pipe;
+  const int crc_cus = ctx->ncu - std::min((int)ctx->opt.wal_pipe_cus, ctx->ncu - 1);
   hipStream_t W = ctx->wal_pw, C = ctx->wal_pc;
   while ((int)ctx->wal_pipe_ev.size() < P) {
     hipEvent_t e;
@@ -2234,8 +1712,8 @@ static int wal_replay_pipelined(lsmck_ctx* ctx, const uint8_t* img, size_t n, vo
   // records to the host, part by part on the SDMA engines (no engines: the
   // whole read-back in wal_finish, after the last part)
   const bool host_recs = !ctx->wal_recs_dev && recs && cap;
-  lsmck_dma::Copier* dc = host_recs && ctx->wal_dma_engines ? dma_copier(ctx) : nullptr;
-  const int E = dc ? std::max(1, std::min(ctx->wal_dma_engines, lsmck_dma::engines(dc))) : 0;
+  lsmck_dma::Copier* dc = host_recs && (int)ctx->opt.wal_dma_engines ? dma_copier(ctx) : nullptr;
+  const int E = dc ? std::max(1, std::min((int)ctx->opt.wal_dma_engines, lsmck_dma::engines(dc))) : 0;
   const bool direct = ctx->wal_recs_direct;
   struct RB {
     lsmck_dma::Job job;
@@ -2246,7 +1724,7 @@ static int wal_replay_pipelined(lsmck_ctx* ctx, const uint8_t* img, size_t n, vo
   int sig_next = 0, derr = 0;
   auto copy_out = [&](size_t a, size_t b) {  // the landing's bytes [a, b) -> the caller's pageable array
     const size_t len = b - a;
-    const unsigned T = len >= (4u << 20) ? std::max(1u, std::min(ctx->stage_threads, 8u)) : 1u;
+    const unsigned T = len >= (4u << 20) ? std::max(1u, std::min((unsigned)ctx->opt.stage_threads, 8u)) : 1u;
     host_pool(ctx).run(T, [&](unsigned t) {
       const size_t x = a + (len * t / T & ~(size_t)4095), y = t + 1 == T ? b : a + (len * (t + 1) / T & ~(size_t)4095);
       if (y > x) memcpy((uint8_t*)recs + x, ctx->h_wrecs + x, y - x);
@@ -2282,15 +1760,15 @@ static int wal_replay_pipelined(lsmck_ctx* ctx, const uint8_t* img, size_t n, vo
     if (direct) {
       land = (uint8_t*)recs + lo * rsz;
     } else {
-      if (hi * rsz > ctx->cap_hwrecs) {  // (the landing grows only with nothing in flight)
+      if (hi * rsz > ctx->h_wrecs.cap()) {  // (the landing grows only with nothing in flight)
         drain(true);
-        if ((rc = ensure_pinned(ctx->pin_node, &ctx->h_wrecs, &ctx->cap_hwrecs, hi * rsz + hi * rsz / 4))) return rc;
+        if ((rc = ctx->h_wrecs.ensure(hi * rsz + hi * rsz / 4, ctx->pin_node))) return rc;
       }
       land = ctx->h_wrecs + lo * rsz;
     }
-    const int chunks = std::max(E, ctx->wal_dma_chunks / 4);
+    const int chunks = std::max(E, (int)ctx->opt.wal_dma_chunks / 4);
     if (sig_next + chunks > lsmck_dma::kMaxSignals) drain(true);
-    const uint8_t* src = c16 ? (const uint8_t*)Wd.recs16 : (const uint8_t*)Wd.recs;
+    const uint8_t* src = c16 ? (const uint8_t*)Wd.recs16.get() : (const uint8_t*)Wd.recs.get();
     RB J;
     J.lo = lo;
     if (lsmck_dma::d2h(dc, land, src + lo * rsz, (hi - lo) * rsz, E, chunks, &J.job, sig_next) != 0) {
@@ -2304,7 +1782,7 @@ static int wal_replay_pipelined(lsmck_ctx* ctx, const uint8_t* img, size_t n, vo
     return 0;
   };
   // part bounds: the first part on every CU (st), the rest in P - 1 parts on W
-  const uint64_t a0 = std::max<uint64_t>(n * (uint64_t)ctx->wal_pipe_first / 64, 1);
+  const uint64_t a0 = std::max<uint64_t>(n * (uint64_t)(int)ctx->opt.wal_pipe_first / 64, 1);
   std::vector<size_t> ends;  // the parts' last records (their spans are their payloads alone)
   uint64_t start = 0;
   size_t at = 0;
@@ -2318,8 +1796,8 @@ static int wal_replay_pipelined(lsmck_ctx* ctx, const uint8_t* img, size_t n, vo
     // (8 waves a SIMD, a segment per 8 lanes): one round of waves, each
     // chain as long as that allows; part 0 on every CU keeps the auto size
     if (k == 1) {
-      const uint64_t lanes = (uint64_t)std::min(ctx->wal_pipe_cus, ctx->ncu - 1) * 4 * 8 * 64 / 8;
-      uint64_t S = ctx->wal_pipe_seg;
+      const uint64_t lanes = (uint64_t)std::min((int)ctx->opt.wal_pipe_cus, ctx->ncu - 1) * 4 * 8 * 64 / 8;
+      uint64_t S = (uint64_t)ctx->opt.wal_pipe_seg;
       if (!S) {
         S = 4096;
         while (S < (16ull << 20) && ((n - a0) / (uint64_t)(P - 1) + S - 1) / S > lanes) S <<= 1;
@@ -2346,14 +1824,14 @@ static int wal_replay_pipelined(lsmck_ctx* ctx, const uint8_t* img, size_t n, vo
       // that outgrows them drains first (wal_grow_hook)
       const size_t est = (size_t)((double)m * ((double)n / (double)std::max<uint64_t>(Pk.tpos, 1)) * 1.15) + 65536;
       const bool dev = ctx->wal_recs_dev_emitted;
-      if ((!dev && !c16 && (rc = ensure_dev_keep(&Wd.recs, &Wd.cap_recs, est, m, st))) ||
-          (!dev && c16 && (rc = ensure_dev_keep(&Wd.recs16, &Wd.cap_recs16, est, m, st))) ||
-          (rc = ensure_dev_keep(&ctx->d_woff, &ctx->cap_woff, est, m, st)) ||
-          (rc = ensure_dev_keep(&ctx->d_wlen, &ctx->cap_wlen, est, m, st)) ||
-          (rc = ensure_dev_keep(&ctx->d_wexp, &ctx->cap_wexp, est, m, st)) ||
-          (rc = ensure_dev_keep(&ctx->d_vcrc, &ctx->cap_vcrc, est, m, st)))
+      if ((!dev && !c16 && (rc = Wd.recs.ensure_keep(est, m, st))) ||
+          (!dev && c16 && (rc = Wd.recs16.ensure_keep(est, m, st))) ||
+          (rc = ctx->d_woff.ensure_keep(est, m, st)) ||
+          (rc = ctx->d_wlen.ensure_keep(est, m, st)) ||
+          (rc = ctx->d_wexp.ensure_keep(est, m, st)) ||
+          (rc = ctx->d_vcrc.ensure_keep(est, m, st)))
         return rc;
-      if (dc && !direct && (rc = ensure_pinned(ctx->pin_node, &ctx->h_wrecs, &ctx->cap_hwrecs, std::min(est, cap) * rsz)))
+      if (dc && !direct && (rc = ctx->h_wrecs.ensure(std::min(est, cap) * rsz, ctx->pin_node)))
         return rc;
     }
     hipEvent_t ev = ctx->wal_pipe_ev[(size_t)k % ctx->wal_pipe_ev.size()];
@@ -2411,14 +1889,14 @@ static int wal_replay_device(lsmck_ctx* ctx, const uint8_t* img, size_t n, void*
   if (so.e != hipSuccess) return hip_error(so.e, "hipStreamWaitEvent(scratch)");
   hipStream_t st = so.st;
   ctx->last_pipe_parts = 0;
-  if (ctx->wal_pipe >= 2 && ctx->wal_seg && !ctx->wal_part_bytes && n >= ctx->wal_pipe_min && n >= 64) {
+  if ((int)ctx->opt.wal_pipe >= 2 && ctx->opt.wal_seg_walk && !(size_t)ctx->opt.wal_part_bytes && n >= (size_t)ctx->opt.wal_pipe_min && n >= 64) {
     rc = wal_replay_pipelined(ctx, img, n, recs, cap, nrec, bad_index, bad_crc, bad_expected, st, tr);
     if (rc != kWalSegDecline && rc != kWalPipeRestart) return rc;
     ctx->last_pipe_parts = 0;  // (a part declined, or outgrew the caller's array: the whole log, unpipelined)
     ctx->wal_recs_dev_emitted = false;
   }
   WalPart P;
-  rc = ctx->wal_seg && !ctx->wal_part_bytes ? wal_seg_walk(ctx, img, n, 0, n, 0, st, tr, &P) : kWalSegDecline;
+  rc = ctx->opt.wal_seg_walk && !(size_t)ctx->opt.wal_part_bytes ? wal_seg_walk(ctx, img, n, 0, n, 0, st, tr, &P) : kWalSegDecline;
   if (rc == 0) {  // the CRC pass over every record, then the compare and the records
     if ((rc = wal_crc_part(ctx, img, 0, P.m, st))) return rc;
     return wal_finish(ctx, img, P.m, P.term, P.tpos, recs, cap, nrec, bad_index, bad_crc, bad_expected, st, tr, 0,
@@ -2427,7 +1905,7 @@ static int wal_replay_device(lsmck_ctx* ctx, const uint8_t* img, size_t n, void*
   if (rc != kWalSegDecline) return rc;
   ctx->last_walk_path = 2;  // candidate doubling: its bitmap, ranks and jump tables
   if ((rc = wal_walk_setup(ctx, n))) return rc;
-  if ((rc = wal_walk_from(ctx, img, n, 0, 0, ctx->wal_part_bytes, marked, st, tr, &P))) return rc;
+  if ((rc = wal_walk_from(ctx, img, n, 0, 0, (size_t)ctx->opt.wal_part_bytes, marked, st, tr, &P))) return rc;
   return wal_finish(ctx, img, P.m, P.term, P.tpos, recs, cap, nrec, bad_index, bad_crc, bad_expected, st, tr);
 }
 
@@ -2448,7 +1926,7 @@ struct WalUpload {
 static int wal_upload_range(lsmck_ctx* ctx, WalUpload& U, size_t lo, size_t hi) {
   auto& W = ctx->wd;
   int rc;
-  const size_t ch = ctx->wal_stage_bytes;
+  const size_t ch = (size_t)ctx->opt.wal_stage_bytes;
   for (size_t o = lo; o < hi; o += ch, U.slot ^= 1) {
     Stage& S = ctx->stage[U.slot];
     const size_t c = std::min(ch, hi - o);
@@ -2456,7 +1934,7 @@ static int wal_upload_range(lsmck_ctx* ctx, WalUpload& U, size_t lo, size_t hi) 
     if (U.direct) {
       HIPCHK(hipMemcpyAsync(ctx->d_wimg + o, U.img + o, c, hipMemcpyHostToDevice, S.s));
     } else {
-      stage_copy(ctx, S.h_pay, U.img + o, c, ctx->stage_threads);
+      stage_copy(ctx, S.h_pay, U.img + o, c, (unsigned)ctx->opt.stage_threads);
       HIPCHK(hipMemcpyAsync(ctx->d_wimg + o, S.h_pay, c, hipMemcpyHostToDevice, S.s));
     }
     HIPCHK(hipEventRecord(S.done, S.s));
@@ -2494,7 +1972,7 @@ struct HostRegistration {
 
 static int wal_upload_prepare(lsmck_ctx* ctx, size_t n, bool direct) {
   int rc;
-  if ((rc = ensure_dev(&ctx->d_wimg, &ctx->cap_wimg, n + 16)) || (rc = wal_walk_setup(ctx, n))) return rc;
+  if ((rc = ctx->d_wimg.ensure(n + 16)) || (rc = wal_walk_setup(ctx, n))) return rc;
   for (int k = 0; k < kHostSlots; ++k) {  // (the upload alternates slots 0 and 1)
     Stage& S = ctx->stage[k];
     if ((rc = stage_init(S))) return rc;
@@ -2502,7 +1980,7 @@ static int wal_upload_prepare(lsmck_ctx* ctx, size_t n, bool direct) {
       HIPCHK(hipStreamSynchronize(S.s));
       S.busy = false;
     }
-    if (!direct && (rc = ensure_pinned(ctx->pin_node, &S.h_pay, &S.cap_h_pay, std::min(n, ctx->wal_stage_bytes)))) return rc;
+    if (!direct && (rc = S.h_pay.ensure(std::min(n, (size_t)ctx->opt.wal_stage_bytes), ctx->pin_node))) return rc;
   }
   return 0;
 }
@@ -2513,7 +1991,7 @@ static int wal_upload(lsmck_ctx* ctx, const uint8_t* img, size_t n, bool pinned)
   DevGuard g(ctx->dev);
   const WalTrace tr;
   std::unique_ptr<HostRegistration> reg;
-  if (!pinned && ctx->wal_register && n >= (1u << 20)) reg.reset(new HostRegistration(img, n));
+  if (!pinned && ctx->opt.wal_register && n >= (1u << 20)) reg.reset(new HostRegistration(img, n));
   WalUpload U{img, n, pinned || (reg && reg->on)};
   int rc;
   if ((rc = wal_upload_prepare(ctx, n, U.direct))) return rc;
@@ -2530,7 +2008,7 @@ static int wal_upload(lsmck_ctx* ctx, const uint8_t* img, size_t n, bool pinned)
 static int wal_records_early(lsmck_ctx* ctx, size_t m, void* recs, size_t cap, hipStream_t st, size_t* done) {
   int rc;
   const size_t rsz = wal_rec_size(ctx);
-  if ((rc = ensure_pinned(ctx->pin_node, &ctx->h_wrecs1, &ctx->cap_hwrecs1, m * rsz))) return rc;
+  if ((rc = ctx->h_wrecs1.ensure(m * rsz, ctx->pin_node))) return rc;
   if (!ctx->wal_rs) HIPCHK(hipStreamCreateWithFlags(&ctx->wal_rs, hipStreamNonBlocking));
   if (!ctx->wal_emit1_ev) HIPCHK(hipEventCreateWithFlags(&ctx->wal_emit1_ev, hipEventDisableTiming));
   HIPCHK(hipEventRecord(ctx->wal_emit1_ev, st));
@@ -2557,14 +2035,14 @@ constexpr int kWalNoSplit = 0x7FFF0002;  // internal: the image is too small to 
 // Caller holds wal_mu.
 static int wal_replay_split(lsmck_ctx* ctx, const uint8_t* img, size_t n, bool pinned, void* recs,
                             size_t cap, size_t* nrec, uint64_t* bad_index, uint32_t* bad_crc, uint32_t* bad_expected) {
-  const size_t ch = ctx->wal_stage_bytes;
+  const size_t ch = (size_t)ctx->opt.wal_stage_bytes;
   const size_t a = (n / 2) / ch * ch;
   if (a < ch || n - a < ch || a >= (1ull << 32)) return kWalNoSplit;
   std::lock_guard<std::mutex> lk(ctx->mu);
   DevGuard g(ctx->dev);
   const WalTrace tr;
   std::unique_ptr<HostRegistration> reg;
-  if (!pinned && ctx->wal_register) reg.reset(new HostRegistration(img, n));
+  if (!pinned && ctx->opt.wal_register) reg.reset(new HostRegistration(img, n));
   // on every return: no DMA from the caller's pages still running (and none
   // from registered pages once they are unregistered, right after this)
   struct SyncStages {
@@ -2603,7 +2081,7 @@ static int wal_replay_split(lsmck_ctx* ctx, const uint8_t* img, size_t n, bool p
       if ((rc = wal_upload_fence(ctx, st))) return rc;
       guard.ok = true;
       WalPart PA;
-      if ((rc = wal_walk_from(ctx, d, n, 0, 0, ctx->wal_part_bytes, false, st, tr, &PA))) return rc;
+      if ((rc = wal_walk_from(ctx, d, n, 0, 0, (size_t)ctx->opt.wal_part_bytes, false, st, tr, &PA))) return rc;
       return wal_finish(ctx, d, PA.m, PA.term, PA.tpos, recs, cap, nrec, bad_index, bad_crc, bad_expected, st, tr);
     }
     if (pr.first) {
@@ -2623,7 +2101,7 @@ static int wal_replay_split(lsmck_ctx* ctx, const uint8_t* img, size_t n, bool p
   // to the prefix scan: mark them again, then walk words [r/64, end) from r
   // (in parts, when the rest's scratch would not fit)
   const uint64_t r = P1.tpos;
-  if (ctx->wal_seg && !ctx->wal_part_bytes) {
+  if (ctx->opt.wal_seg_walk && !(size_t)ctx->opt.wal_part_bytes) {
     rc = wal_seg_walk(ctx, d, n, r, n, P1.m, st, tr, &P2);
     if (rc == 0) {
       if ((rc = wal_crc_part(ctx, d, P1.m, P2.m - P1.m, st))) return rc;
@@ -2635,8 +2113,29 @@ static int wal_replay_split(lsmck_ctx* ctx, const uint8_t* img, size_t n, bool p
   ctx->last_walk_path = 2;
   if (r < a && (rc = lsmk_wal_mark_range(d, n, r & ~(uint64_t)63, a, ctx->wd.bits, ctx->wd.pre, st)))
     return launch_rc(rc, "wal mark kernel");
-  if ((rc = wal_walk_from(ctx, d, n, r, P1.m, ctx->wal_part_bytes, true, st, tr, &P2))) return rc;
+  if ((rc = wal_walk_from(ctx, d, n, r, P1.m, (size_t)ctx->opt.wal_part_bytes, true, st, tr, &P2))) return rc;
   return wal_finish(ctx, d, P2.m, P2.term, P2.tpos, recs, cap, nrec, bad_index, bad_crc, bad_expected, st, tr, done);
+}
+
+// A host-form builder call's inputs, uploaded whole on st into ctx->in: the
+// key arena, the value arena (not when it is the key arena again, nor when the
+// caller's kernels read no value: need_vals) and the n commands.  *dk, *dv
+// and *dc come in as the caller's pointers and leave as the device copies'.
+// Caller holds ctx->mu.
+static int stage_inputs(lsmck_ctx* ctx, const uint8_t** dk, size_t keys_bytes, const uint8_t** dv, size_t vals_bytes,
+                        bool need_vals, const lsmck_wal_cmd** dc, size_t n, hipStream_t st) {
+  auto& I = ctx->in;
+  int rc;
+  const bool own_vals = need_vals && !(*dk == *dv && keys_bytes == vals_bytes);
+  if ((rc = I.keys.ensure(keys_bytes)) || (rc = I.cmds.ensure(n)) || (own_vals && (rc = I.vals.ensure(vals_bytes))))
+    return rc;
+  if (keys_bytes) HIPCHK(hipMemcpyAsync(I.keys, *dk, keys_bytes, hipMemcpyHostToDevice, st));
+  if (own_vals && vals_bytes) HIPCHK(hipMemcpyAsync(I.vals, *dv, vals_bytes, hipMemcpyHostToDevice, st));
+  if (n) HIPCHK(hipMemcpyAsync(I.cmds, *dc, n * sizeof(lsmck_wal_cmd), hipMemcpyHostToDevice, st));
+  *dk = I.keys;
+  *dv = own_vals ? I.vals.get() : need_vals ? I.keys.get() : *dv;
+  *dc = I.cmds;
+  return 0;
 }
 
 extern "C" {
@@ -2670,32 +2169,17 @@ int lsmck_wal_encode_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_byte
   const bool dev = (flags & LSMCK_DEVICE) != 0;
   const uint8_t *dk = keys, *dv = vals;
   const lsmck_wal_cmd* dc = cmds;
-  if (!dev) {  // staged whole: the arenas (once when they are one buffer) and the commands
-    const bool same = keys == vals && keys_bytes == vals_bytes;
-    if ((rc = ensure_dev(&E.keys, &E.cap_keys, keys_bytes)) || (rc = ensure_dev(&E.cmds, &E.cap_cmds, n)) ||
-        (!same && (rc = ensure_dev(&E.vals, &E.cap_vals, vals_bytes))))
-      return rc;
-    if (keys_bytes) HIPCHK(hipMemcpyAsync(E.keys, keys, keys_bytes, hipMemcpyHostToDevice, st));
-    if (!same && vals_bytes) HIPCHK(hipMemcpyAsync(E.vals, vals, vals_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(E.cmds, cmds, n * sizeof(lsmck_wal_cmd), hipMemcpyHostToDevice, st));
-    dk = E.keys;
-    dv = same ? E.keys : E.vals;
-    dc = E.cmds;
-  }
-  if ((rc = ensure_dev(&E.off, &E.cap_off, n + 1)) ||
-      (rc = ensure_dev(&E.bsum, &E.cap_bsum, (size_t)lsmk_wal_encode_scan_blocks(n) + 1)))
-    return rc;
+  if (!dev && (rc = stage_inputs(ctx, &dk, keys_bytes, &dv, vals_bytes, true, &dc, n, st))) return rc;
+  if ((rc = E.off.ensure(n + 1)) || (rc = E.bsum.ensure((size_t)lsmk_wal_encode_scan_blocks(n) + 1))) return rc;
   // 1. sizes, validation, offsets; the total and the first invalid command come back
   unsigned long long* info = ctx->d_verify + 2;
   HIPCHK(hipMemsetAsync(info, 0xFF, 16, st));
-  const bool timed = ctx->enc_time;
-  hipEvent_t* ev = ctx->enc_ev;
-  if (timed && !ev[0])
-    for (int k = 0; k < 6; ++k) HIPCHK(hipEventCreate(&ev[k]));
-  if (timed) HIPCHK(hipEventRecord(ev[0], st));
+  StageTimer& T = ctx->enc_timer;
+  T.begin(ctx->opt.wal_encode_time);
+  HIPCHK(T.mark(0, st));
   if ((rc = lsmk_wal_encode_scan(dc, n, keys_bytes, vals_bytes, E.off, E.bsum, info, st)))
     return launch_rc(rc, "wal encode scan kernels");
-  if (timed) HIPCHK(hipEventRecord(ev[1], st));
+  HIPCHK(T.mark(1, st));
   HIPCHK(hipMemcpyAsync(ctx->h_verify + 2, info, 16, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   const uint64_t bad = ctx->h_verify[2], total = ctx->h_verify[3];
@@ -2707,34 +2191,25 @@ int lsmck_wal_encode_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_byte
   if (cap < total) return lsmck_host::set_error(LSMCK_ENOSPC, "wal encode: the image buffer is too small");
   uint8_t* di = img;
   if (!dev) {
-    if ((rc = ensure_dev(&E.img, &E.cap_img, (size_t)total))) return rc;
+    if ((rc = E.img.ensure((size_t)total))) return rc;
     di = E.img;
   }
-  if ((rc = ensure_dev(&ctx->d_woff, &ctx->cap_woff, n)) || (rc = ensure_dev(&ctx->d_wlen, &ctx->cap_wlen, n)) ||
-      (rc = ensure_dev(&ctx->d_vcrc, &ctx->cap_vcrc, n)))
-    return rc;
+  if ((rc = ctx->d_woff.ensure(n)) || (rc = ctx->d_wlen.ensure(n)) || (rc = ctx->d_vcrc.ensure(n))) return rc;
   // 2. gather  3. payload CRCs over the image  4. stamp
-  if (timed) HIPCHK(hipEventRecord(ev[2], st));
+  HIPCHK(T.mark(2, st));
   if ((rc = lsmk_wal_encode_gather(dk, dv, dc, n, E.off, di, total, st))) return launch_rc(rc, "wal encode gather kernel");
-  if (timed) HIPCHK(hipEventRecord(ev[3], st));
+  HIPCHK(T.mark(3, st));
   if ((rc = lsmk_wal_encode_desc(dc, n, E.off, ctx->d_woff, ctx->d_wlen, st)))
     return launch_rc(rc, "wal encode descriptor kernel");
   if ((rc = crc_desc_device(ctx, ctx->scratch, di, ctx->d_woff, ctx->d_wlen, n, ctx->d_vcrc, st))) return rc;
-  if (timed) HIPCHK(hipEventRecord(ev[4], st));
+  HIPCHK(T.mark(4, st));
   if ((rc = lsmk_wal_encode_stamp(di, E.off, ctx->d_vcrc, n, st))) return launch_rc(rc, "wal encode stamp kernel");
-  if (timed) HIPCHK(hipEventRecord(ev[5], st));
+  HIPCHK(T.mark(5, st));
   if (rec_off)
     HIPCHK(hipMemcpyAsync(rec_off, E.off, n * 8, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
   if (!dev) HIPCHK(hipMemcpyAsync(img, di, (size_t)total, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  if (timed) {
-    const int pair[4][2] = {{0, 1}, {2, 3}, {3, 4}, {4, 5}};
-    for (int k = 0; k < 4; ++k) {
-      float ms = 0;
-      HIPCHK(hipEventElapsedTime(&ms, ev[pair[k][0]], ev[pair[k][1]]));
-      ctx->enc_ns[k] = (long)((double)ms * 1e6);
-    }
-  }
+  HIPCHK(T.finish4());
   return 0;
 }
 
@@ -2784,27 +2259,13 @@ int lsmck_sstable_encode_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_
   const bool dev = (flags & LSMCK_DEVICE) != 0;
   const uint8_t *dk = keys, *dv = vals;
   const lsmck_wal_cmd* dc = ents;
-  if (!dev) {  // staged whole: the arenas (once when they are one buffer) and the entries
-    const bool same = keys == vals && keys_bytes == vals_bytes;
-    if ((rc = ensure_dev(&S.keys, &S.cap_keys, keys_bytes)) || (rc = ensure_dev(&S.ents, &S.cap_ents, n)) ||
-        (!same && (rc = ensure_dev(&S.vals, &S.cap_vals, vals_bytes))))
-      return rc;
-    if (keys_bytes) HIPCHK(hipMemcpyAsync(S.keys, keys, keys_bytes, hipMemcpyHostToDevice, st));
-    if (!same && vals_bytes) HIPCHK(hipMemcpyAsync(S.vals, vals, vals_bytes, hipMemcpyHostToDevice, st));
-    if (n) HIPCHK(hipMemcpyAsync(S.ents, ents, n * sizeof(lsmck_wal_cmd), hipMemcpyHostToDevice, st));
-    dk = S.keys;
-    dv = same ? S.keys : S.vals;
-    dc = S.ents;
-  }
+  if (!dev && (rc = stage_inputs(ctx, &dk, keys_bytes, &dv, vals_bytes, true, &dc, n, st))) return rc;
   const size_t nb = (size_t)std::max(lsmk_sst_scan_blocks(n), lsmk_sst_scan_blocks(nitems)) + 1;
-  if ((rc = ensure_dev(&S.off, &S.cap_off, n + 1)) || (rc = ensure_dev(&S.bsum, &S.cap_bsum, nb)) ||
-      (rc = ensure_dev(&S.first, &S.cap_first, n)) || (rc = ensure_dev(&S.tf, &S.cap_tf, ntab + 1)) ||
-      (rc = ensure_dev(&S.ibase, &S.cap_ibase, ntab + 1)) ||
-      (rc = ensure_dev(&S.item_tab, &S.cap_item_tab, (size_t)nitems)) ||
-      (rc = ensure_dev(&S.item_ent, &S.cap_item_ent, (size_t)nitems)) ||
-      (rc = ensure_dev(&S.ioff, &S.cap_ioff, (size_t)nitems + 1)) || (rc = ensure_dev(&S.spans, &S.cap_spans, ntab)) ||
-      (rc = ensure_dev(&S.doff, &S.cap_doff, ntab)) || (rc = ensure_dev(&S.dlen, &S.cap_dlen, ntab)) ||
-      (rc = ensure_dev(&S.xoff, &S.cap_xoff, ntab)) || (rc = ensure_dev(&S.xlen, &S.cap_xlen, ntab)))
+  if ((rc = S.off.ensure(n + 1)) || (rc = S.bsum.ensure(nb)) || (rc = S.first.ensure(n)) ||
+      (rc = S.tf.ensure(ntab + 1)) || (rc = S.ibase.ensure(ntab + 1)) || (rc = S.item_tab.ensure((size_t)nitems)) ||
+      (rc = S.item_ent.ensure((size_t)nitems)) || (rc = S.ioff.ensure((size_t)nitems + 1)) ||
+      (rc = S.spans.ensure(ntab)) || (rc = S.doff.ensure(ntab)) || (rc = S.dlen.ensure(ntab)) ||
+      (rc = S.xoff.ensure(ntab)) || (rc = S.xlen.ensure(ntab)))
     return rc;
   HIPCHK(hipMemcpyAsync(S.tf, table_first, (ntab + 1) * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(S.ibase, ibase.data(), (ntab + 1) * 8, hipMemcpyHostToDevice, st));
@@ -2817,11 +2278,9 @@ int lsmck_sstable_encode_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_
   unsigned long long* info = ctx->d_verify + 4;
   HIPCHK(hipMemsetAsync(info, 0xFF, 32, st));
   if (n) HIPCHK(hipMemsetAsync(S.first, 0, n, st));
-  const bool timed = ctx->sst_time;
-  hipEvent_t* ev = ctx->sst_ev;
-  if (timed && !ev[0])
-    for (int k = 0; k < 6; ++k) HIPCHK(hipEventCreate(&ev[k]));
-  if (timed) HIPCHK(hipEventRecord(ev[0], st));
+  StageTimer& T = ctx->sst_timer;
+  T.begin(ctx->opt.sst_encode_time);
+  HIPCHK(T.mark(0, st));
   const unsigned hash = (data_sha ? 1u : 0u) | (index_sha ? 2u : 0u);
   if ((rc = lsmk_sst_sizes(dc, n, keys_bytes, vals_bytes, S.off, S.bsum, info, st)))
     return launch_rc(rc, "sstable encode size / scan kernels");
@@ -2832,7 +2291,7 @@ int lsmck_sstable_encode_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_
   if ((rc = lsmk_sst_spans(S.tf, S.ibase, ntab, S.off, S.ioff, S.spans, S.doff, S.dlen, S.xoff, S.xlen, hash, info,
                            st)))
     return launch_rc(rc, "sstable encode span kernel");
-  if (timed) HIPCHK(hipEventRecord(ev[1], st));
+  HIPCHK(T.mark(1, st));
   HIPCHK(hipMemcpyAsync(ctx->h_verify + 4, info, 32, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   const uint64_t bad = ctx->h_verify[4], total = ctx->h_verify[5], bad_tab = ctx->h_verify[6],
@@ -2854,23 +2313,23 @@ int lsmck_sstable_encode_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_
   if ((total && !data) || (itotal && !index)) return lsmck_host::set_error(LSMCK_EINVAL, "null data or index buffer");
   uint8_t *dd = data, *dx = index, *dsd = data_sha, *dsx = index_sha;
   if (!dev) {
-    if ((rc = ensure_dev(&S.data, &S.cap_data, (size_t)total)) || (rc = ensure_dev(&S.index, &S.cap_index, (size_t)itotal)) ||
-        (rc = ensure_dev(&S.sha, &S.cap_sha, 64 * ntab)))
+    if ((rc = S.data.ensure((size_t)total)) || (rc = S.index.ensure((size_t)itotal)) ||
+        (rc = S.sha.ensure(64 * ntab)))
       return rc;
     dd = S.data, dx = S.index;
-    dsd = data_sha ? S.sha : nullptr;
+    dsd = data_sha ? S.sha.get() : nullptr;
     dsx = index_sha ? S.sha + 32 * ntab : nullptr;
   }
   // 4. the data gather  5. the index writer  6. the digests
-  if (timed) HIPCHK(hipEventRecord(ev[2], st));
+  HIPCHK(T.mark(2, st));
   if ((rc = lsmk_sst_gather(dk, dv, dc, n, S.off, dd, total, st))) return launch_rc(rc, "sstable encode gather kernel");
-  if (timed) HIPCHK(hipEventRecord(ev[3], st));
+  HIPCHK(T.mark(3, st));
   if ((rc = lsmk_sst_index_write(S.item_tab, S.item_ent, nitems, S.tf, dc, dk, S.off, S.ioff, dx, st)))
     return launch_rc(rc, "sstable encode index kernel");
-  if (timed) HIPCHK(hipEventRecord(ev[4], st));
+  HIPCHK(T.mark(4, st));
   if (ntab && dsd && (rc = sha_device(ctx, ctx->scratch, dd, S.doff, S.dlen, 0, 0, ntab, dsd, st))) return rc;
   if (ntab && dsx && (rc = sha_device(ctx, ctx->scratch, dx, S.xoff, S.xlen, 0, 0, ntab, dsx, st))) return rc;
-  if (timed) HIPCHK(hipEventRecord(ev[5], st));
+  HIPCHK(T.mark(5, st));
   if (spans && ntab)
     HIPCHK(hipMemcpyAsync(spans, S.spans, ntab * sizeof(lsmck_sstable_span),
                           dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
@@ -2881,14 +2340,7 @@ int lsmck_sstable_encode_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_
     if (dsx) HIPCHK(hipMemcpyAsync(index_sha, dsx, 32 * ntab, hipMemcpyDeviceToHost, st));
   }
   HIPCHK(hipStreamSynchronize(st));
-  if (timed) {
-    const int pair[4][2] = {{0, 1}, {2, 3}, {3, 4}, {4, 5}};
-    for (int k = 0; k < 4; ++k) {
-      float ms = 0;
-      HIPCHK(hipEventElapsedTime(&ms, ev[pair[k][0]], ev[pair[k][1]]));
-      ctx->sst_ns[k] = (long)((double)ms * 1e6);
-    }
-  }
+  HIPCHK(T.finish4());
   return 0;
 }
 
@@ -2925,42 +2377,27 @@ int lsmck_memtable_build(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes,
   if (so.e != hipSuccess) return hip_error(so.e, "hipStreamWaitEvent(scratch)");
   auto& M = ctx->mem;
   const bool dev = (flags & LSMCK_DEVICE) != 0;
-  const uint8_t* dk = keys;
+  const uint8_t *dk = keys, *dv = vals;
   const lsmck_wal_cmd* dc = cmds;
-  if (!dev) {  // staged whole: the key arena and the commands (no kernel reads a value)
-    if ((rc = ensure_dev(&M.keys, &M.cap_keys, keys_bytes)) || (rc = ensure_dev(&M.cmds, &M.cap_cmds, n))) return rc;
-    if (keys_bytes) HIPCHK(hipMemcpyAsync(M.keys, keys, keys_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(M.cmds, cmds, n * sizeof(lsmck_wal_cmd), hipMemcpyHostToDevice, st));
-    dk = M.keys;
-    dc = M.cmds;
-  }
+  // (no kernel reads a value: the value arena stays where it is)
+  if (!dev && (rc = stage_inputs(ctx, &dk, keys_bytes, &dv, vals_bytes, false, &dc, n, st))) return rc;
   lsmck::MemWs W;
-  if ((rc = ensure_dev(&M.ws, &M.cap_ws, lsmk_mem_carve(nullptr, n, nullptr))) ||
-      (rc = ensure_dev(&M.info, &M.cap_info, 4)))
+  if ((rc = M.ws.ensure(lsmk_mem_carve(nullptr, n, nullptr))) || (rc = M.info.ensure(4)) ||
+      (rc = M.h_info.ensure(8, -1)))
     return rc;
-  if (!M.h_info) HIPCHK(hipHostMalloc((void**)&M.h_info, 64, hipHostMallocDefault));
   (void)lsmk_mem_carve(M.ws, n, &W);
-  const bool timed = ctx->mem_time;
-  hipEvent_t* ev = ctx->mem_ev;
-  if (timed && !ev[0])
-    for (int k = 0; k < 7; ++k) HIPCHK(hipEventCreate(&ev[k]));
-  double ns[4] = {0, 0, 0, 0};
-  auto span = [&](int a, int b, double* into) -> int {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, ev[a], ev[b]));
-    *into += (double)ms * 1e6;
-    return 0;
-  };
+  StageTimer& T = ctx->mem_timer;
+  T.begin(ctx->opt.mem_build_time);
   // 1. validate; its word comes back before any kernel reads a key
   unsigned long long* info = M.info;  // [0] first invalid, [1] active count, [2] mem_bytes
   HIPCHK(hipMemsetAsync(info, 0xFF, 8, st));
   HIPCHK(hipMemsetAsync(info + 1, 0, 16, st));
-  if (timed) HIPCHK(hipEventRecord(ev[0], st));
+  HIPCHK(T.mark(0, st));
   if ((rc = lsmk_mem_validate(dc, n, keys_bytes, vals_bytes, info, st))) return launch_rc(rc, "memtable validate kernel");
-  if (timed) HIPCHK(hipEventRecord(ev[1], st));
+  HIPCHK(T.mark(1, st));
   HIPCHK(hipMemcpyAsync(M.h_info, info, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  if (timed && (rc = span(0, 1, &ns[0]))) return rc;
+  HIPCHK(T.span(0, 1, 0));
   if (M.h_info[0] != ~0ull) {
     if (bad_index) *bad_index = M.h_info[0];
     return lsmck_host::set_error(LSMCK_EINVAL, "memtable build: invalid command (type or source range)");
@@ -2975,17 +2412,18 @@ int lsmck_memtable_build(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes,
     size_t tmp = 0;
     if ((rc = lsmk_mem_sort_regroup(&W, m, r, group_bits, nullptr, &tmp, nullptr, st)))
       return launch_rc(rc, "memtable sort (temporary storage size)");
-    if ((rc = ensure_dev(&M.tmp, &M.cap_tmp, tmp))) return rc;
-    if (timed) HIPCHK(hipEventRecord(ev[2], st));
+    if ((rc = M.tmp.ensure(tmp))) return rc;
+    HIPCHK(T.mark(2, st));
     if ((rc = lsmk_mem_chunk(&W, dk, dc, m, r, st))) return launch_rc(rc, "memtable chunk kernel");
-    if (timed) HIPCHK(hipEventRecord(ev[3], st));
-    tmp = M.cap_tmp;
+    HIPCHK(T.mark(3, st));
+    tmp = M.tmp.cap();
     if ((rc = lsmk_mem_sort_regroup(&W, m, r, group_bits, M.tmp, &tmp, info + 1, st)))
       return launch_rc(rc, "memtable sort / regroup kernels");
-    if (timed) HIPCHK(hipEventRecord(ev[4], st));
+    HIPCHK(T.mark(4, st));
     HIPCHK(hipMemcpyAsync(M.h_info + 1, info + 1, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (timed && ((rc = span(2, 3, &ns[1])) || (rc = span(3, 4, &ns[2])))) return rc;
+    HIPCHK(T.span(2, 3, 1));
+    HIPCHK(T.span(3, 4, 2));
     if (M.h_info[1] > m) return lsmck_host::set_error(LSMCK_EIO, "memtable build: active count grew");
     m = M.h_info[1];
     std::swap(W.apos, W.apos2);
@@ -2994,9 +2432,9 @@ int lsmck_memtable_build(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes,
   // 3. resolve; the count and the bytes come back before ents and src are written
   size_t tmp = 0;
   if ((rc = lsmk_mem_resolve(&W, dc, n, nullptr, &tmp, nullptr, st))) return launch_rc(rc, "memtable scan (size)");
-  if ((rc = ensure_dev(&M.tmp, &M.cap_tmp, tmp))) return rc;
-  tmp = M.cap_tmp;
-  if (timed) HIPCHK(hipEventRecord(ev[5], st));
+  if ((rc = M.tmp.ensure(tmp))) return rc;
+  tmp = M.tmp.cap();
+  HIPCHK(T.mark(5, st));
   if ((rc = lsmk_mem_resolve(&W, dc, n, M.tmp, &tmp, info + 2, st))) return launch_rc(rc, "memtable resolve kernels");
   M.h_info[3] = 0;
   HIPCHK(hipMemcpyAsync(M.h_info + 2, info + 2, 8, hipMemcpyDeviceToHost, st));
@@ -3010,22 +2448,19 @@ int lsmck_memtable_build(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes,
   lsmck_wal_cmd* de = ents;
   uint32_t* ds = src;
   if (!dev && live) {
-    if ((rc = ensure_dev(&M.ents, &M.cap_ents, (size_t)live)) || (src && (rc = ensure_dev(&M.src, &M.cap_src, (size_t)live))))
-      return rc;
+    if ((rc = M.ents.ensure((size_t)live)) || (src && (rc = M.src.ensure((size_t)live)))) return rc;
     de = M.ents;
-    ds = src ? M.src : nullptr;
+    ds = src ? M.src.get() : nullptr;
   }
   if (live && (rc = lsmk_mem_emit(&W, dc, n, de, ds, st))) return launch_rc(rc, "memtable emit kernel");
-  if (timed) HIPCHK(hipEventRecord(ev[6], st));
+  HIPCHK(T.mark(6, st));
   if (!dev && live) {
     HIPCHK(hipMemcpyAsync(ents, de, (size_t)live * sizeof(lsmck_wal_cmd), hipMemcpyDeviceToHost, st));
     if (src) HIPCHK(hipMemcpyAsync(src, ds, (size_t)live * 4, hipMemcpyDeviceToHost, st));
   }
   HIPCHK(hipStreamSynchronize(st));
-  if (timed) {
-    if ((rc = span(5, 6, &ns[3]))) return rc;
-    for (int k = 0; k < 4; ++k) ctx->mem_ns[k] = (long)ns[k];
-  }
+  HIPCHK(T.span(5, 6, 3));
+  T.finish();
   return 0;
 }
 
@@ -3074,7 +2509,7 @@ static int wal_replay_verify(lsmck_ctx* ctx, const uint8_t* wal, size_t n, unsig
   // LSMCK_RECS_PINNED: the records go by DMA into the caller's pinned array
   // (read by wal_finish under wal_mu; the host walk ignores it)
   const bool recs_pinned = (flags & LSMCK_RECS_PINNED) != 0;
-  const bool gpu_walk = (flags & LSMCK_DEVICE) && ctx->wal_gpu_walk && !(flags & kWalNoGpuWalk);
+  const bool gpu_walk = (flags & LSMCK_DEVICE) && ctx->opt.wal_gpu_walk && !(flags & kWalNoGpuWalk);
   if (flags & LSMCK_RECS_DEVICE) {
     if (recs_pinned) return lsmck_host::set_error(LSMCK_EINVAL, "LSMCK_RECS_DEVICE with LSMCK_RECS_PINNED");
     unsigned more = 0;
@@ -3107,14 +2542,14 @@ static int wal_replay_verify(lsmck_ctx* ctx, const uint8_t* wal, size_t n, unsig
     rc = wal_replay_device(ctx, wal, n, recs, cap, nrec, bad_index, bad_crc, bad_expected);
     if (rc != kWalHostWalk) return rc;
     // (the GPU walk declined: the image is copied back and walked on the host below)
-  } else if (!(flags & LSMCK_DEVICE) && ctx->wal_upload_min && n >= ctx->wal_upload_min) {
+  } else if (!(flags & LSMCK_DEVICE) && (size_t)ctx->opt.wal_upload_min && n >= (size_t)ctx->opt.wal_upload_min) {
     // Host image: one upload (~36 GiB/s through the staging slots) and the GPU
     // header walk, instead of the serial host walk (~12 GiB/s) -- the records
     // and offsets are the same, they index the caller's image
     std::lock_guard<std::mutex> wl(ctx->wal_mu);
     WalCallRecs wc(ctx, compact, recs_pinned, nullptr, 0);
     const bool pinned = (flags & LSMCK_HOST_PINNED) != 0;
-    rc = ctx->wal_split ? wal_replay_split(ctx, wal, n, pinned, recs, cap, nrec, bad_index, bad_crc, bad_expected)
+    rc = ctx->opt.wal_split ? wal_replay_split(ctx, wal, n, pinned, recs, cap, nrec, bad_index, bad_crc, bad_expected)
                         : kWalNoSplit;
     if (rc == kWalNoSplit) {
       if ((rc = wal_upload(ctx, wal, n, pinned))) return rc;
@@ -3131,7 +2566,7 @@ static int wal_replay_verify(lsmck_ctx* ctx, const uint8_t* wal, size_t n, unsig
   if (flags & LSMCK_DEVICE) {
     wal_lk.lock();
     DevGuard g(ctx->dev);
-    rc = ensure_pinned(ctx->pin_node, &ctx->wal_host, &ctx->wal_host_cap, n);
+    rc = ctx->wal_host.ensure(n, ctx->pin_node);
     if (rc) return rc;
     if (n) HIPCHK(hipMemcpy(ctx->wal_host, wal, n, hipMemcpyDeviceToHost));
     h = ctx->wal_host;
@@ -3150,14 +2585,14 @@ static int wal_replay_verify(lsmck_ctx* ctx, const uint8_t* wal, size_t n, unsig
   // previous header's lengths -- so without help every header is one DRAM
   // round trip (~140 ns, 500k records in 72 ms, 1.7 GiB/s).  Every line up to
   // `dist` bytes ahead is prefetched, turning the chain into a stream.
-  const size_t dist = ctx->wal_prefetch;
+  const size_t dist = (size_t)ctx->opt.wal_prefetch;
   size_t pf = 0;
   // Host image: the CRCs of the records walked so far run as a batch on a
   // helper thread while the walk goes on.  Each batch takes its own copy of
   // its descriptors (the vectors move as they grow), batches serialise on the
   // context's lock, and every helper is joined before the function returns
   // (a std::async future's destructor waits).
-  const bool overlap = !(flags & LSMCK_DEVICE) && ctx->wal_chunk;
+  const bool overlap = !(flags & LSMCK_DEVICE) && (size_t)ctx->opt.wal_chunk_bytes;
   struct Part {
     size_t r0, r1;
     struct Out {
@@ -3211,7 +2646,7 @@ static int wal_replay_verify(lsmck_ctx* ctx, const uint8_t* wal, size_t n, unsig
     rk.push_back(klen);
     rv.push_back(vlen);
     pos += hdr + got;
-    if (overlap && (chunk_bytes += got) >= ctx->wal_chunk) launch(poff.size());
+    if (overlap && (chunk_bytes += got) >= (size_t)ctx->opt.wal_chunk_bytes) launch(poff.size());
   }
   size_t m = poff.size();
   if (overlap && chunk_r0 < m) launch(m);
@@ -3224,9 +2659,9 @@ static int wal_replay_verify(lsmck_ctx* ctx, const uint8_t* wal, size_t n, unsig
       // only the two counts come back
       std::lock_guard<std::mutex> lk(ctx->mu);
       DevGuard g(ctx->dev);
-      if ((rc = ensure_pinned(ctx->pin_node, &ctx->h_woff, &ctx->cap_hwoff, m)) || (rc = ensure_pinned(ctx->pin_node, &ctx->h_wlen, &ctx->cap_hwlen, m)) ||
-          (rc = ensure_pinned(ctx->pin_node, &ctx->h_wexp, &ctx->cap_hwexp, m)) || (rc = ensure_dev(&ctx->d_woff, &ctx->cap_woff, m)) ||
-          (rc = ensure_dev(&ctx->d_wlen, &ctx->cap_wlen, m)) || (rc = ensure_dev(&ctx->d_wexp, &ctx->cap_wexp, m)))
+      if ((rc = ctx->h_woff.ensure(m, ctx->pin_node)) || (rc = ctx->h_wlen.ensure(m, ctx->pin_node)) ||
+          (rc = ctx->h_wexp.ensure(m, ctx->pin_node)) || (rc = ctx->d_woff.ensure(m)) ||
+          (rc = ctx->d_wlen.ensure(m)) || (rc = ctx->d_wexp.ensure(m)))
         return rc;
       ScratchOrder so(ctx, ctx->stream0);
       if (so.e != hipSuccess) return hip_error(so.e, "hipStreamWaitEvent(scratch)");
@@ -3464,21 +2899,21 @@ static int verify_tables(lsmck_ctx* ctx, const char* const* data_paths, const ch
     }
   } want_th;
   // (a compaction tick's 142k-table batch: 4 threads 0.82-0.86 s, 2 0.90-0.94 s, 8 0.84-0.99 s; profiles/r05/tk)
-  const unsigned jt = ctx->tree_json_threads ? ctx->tree_json_threads : (n >= 16384 ? 4u : 2u);
+  const unsigned jt = (unsigned)ctx->opt.tree_json_threads ? (unsigned)ctx->opt.tree_json_threads : (n >= 16384 ? 4u : 2u);
   for (unsigned t = 0; t < (n >= 64 ? jt : n ? 1u : 0u); ++t)
     want_th.t.emplace_back([&]() {
       for (size_t i; (i = want_next.fetch_add(1, std::memory_order_relaxed)) < n;)
         want_rc[i] = lsmck_host::read_checksum_json(checksum_paths[i], &want_i[i], &want_d[i]);
     });
-  const uint32_t active_max = ctx->tree_active ? ctx->tree_active : kTreeActive;
-  const uint32_t slice = ctx->tree_slice ? ctx->tree_slice : kTreeSlice;
+  const uint32_t active_max = (uint32_t)ctx->opt.tree_active_files ? (uint32_t)ctx->opt.tree_active_files : kTreeActive;
+  const uint32_t slice = (uint32_t)ctx->opt.tree_slice_bytes ? (uint32_t)ctx->opt.tree_slice_bytes : kTreeSlice;
   std::vector<uint8_t> dig(32 * std::max<size_t>(nf, 1), 0);
   // Large files are hashed on host threads (SHA-NI where the CPU has it,
   // ~1.5-2 GB/s per thread) while the GPU streams the rest: SHA-256 is
   // sequential inside a file, so one file is one GPU lane at ~16 MB/s -- a
   // 230 MB table alone would hold the stream open for 14 s.  The GPU admits
   // the remaining files largest first, so no large file starts at the tail.
-  const uint64_t cpu_min = ctx->tree_cpu_file ? ctx->tree_cpu_file : kTreeCpuFile;
+  const uint64_t cpu_min = (uint64_t)ctx->opt.tree_cpu_file_bytes ? (uint64_t)ctx->opt.tree_cpu_file_bytes : kTreeCpuFile;
   std::vector<size_t> gpu_order, cpu_files;
   for (size_t f = 0; f < nf; ++f) {
     if (ferr[f]) continue;
@@ -3527,8 +2962,8 @@ static int verify_tables(lsmck_ctx* ctx, const char* const* data_paths, const ch
     for (auto& S : ctx->stage)
       if ((rc = stage_init(S))) return rc;
     auto& T = ctx->tree;
-    if ((rc = ensure_dev(&T.state, &T.cap_state, 8ull * active_max))) return rc;
-    if ((rc = ensure_dev(&T.digests, &T.cap_digests, 32 * std::max<size_t>(nf, 1)))) return rc;
+    if ((rc = T.state.ensure(8ull * active_max))) return rc;
+    if ((rc = T.digests.ensure(32 * std::max<size_t>(nf, 1)))) return rc;
     if (!T.kernel_done) HIPCHK(hipEventCreateWithFlags(&T.kernel_done, hipEventDisableTiming));
     // active slots: file index and bytes already scheduled
     std::vector<size_t> slot_file(active_max, SIZE_MAX);
@@ -3539,12 +2974,12 @@ static int verify_tables(lsmck_ctx* ctx, const char* const* data_paths, const ch
     // the rounds cycle through ns slots: a round's reads wait for the round
     // ns back (its slot), so with three the reads of round r + 2 overlap the
     // upload and hashing of rounds r and r + 1
-    const uint32_t ns = ctx->tree_stages;
+    const uint32_t ns = (uint32_t)ctx->opt.tree_stages;
     bool busy[3] = {false, false, false}, any_kernel = false;
     uint32_t sl = 0;
     std::vector<uint64_t> rd_off;  // per slice: offset inside its file
     SlotFds fds(active_max);
-    if (ctx->tree_open >= 0) fds.cached = (uint32_t)std::min<long>(fds.cached, ctx->tree_open);
+    if (ctx->opt.tree_open_files >= 0) fds.cached = (uint32_t)std::min<long>(fds.cached, ctx->opt.tree_open_files);
     tm->fds_cached = fds.cached;
     for (;;) {
       // admit files into free slots
@@ -3594,10 +3029,10 @@ static int verify_tables(lsmck_ctx* ctx, const char* const* data_paths, const ch
         }
       }
       const size_t cnt = sv.size();
-      if ((rc = ensure_pinned(ctx->pin_node, &S.h_pay, &S.cap_h_pay, pay + 16, true))) return rc;
-      if ((rc = ensure_pinned(ctx->pin_node, &S.h_slices, &S.cap_h_slices, cnt, true))) return rc;
-      if ((rc = ensure_dev(&S.d_pay, &S.cap_d_pay, pay + 16))) return rc;
-      if ((rc = ensure_dev(&S.d_slices, &S.cap_d_slices, cnt))) return rc;
+      if ((rc = S.h_pay.ensure(pay + 16, ctx->pin_node, true))) return rc;
+      if ((rc = S.h_slices.ensure(cnt, ctx->pin_node, true))) return rc;
+      if ((rc = S.d_pay.ensure(pay + 16))) return rc;
+      if ((rc = S.d_slices.ensure(cnt))) return rc;
       memcpy(S.h_slices, sv.data(), cnt * sizeof(lsmck::ShaSlice));
       // read the slices (overlaps the other slot's GPU work, already queued)
       clk.lap();
@@ -3613,7 +3048,7 @@ static int verify_tables(lsmck_ctx* ctx, const char* const* data_paths, const ch
           if (e) ferr[d.msg] = e == SlotFds::kOpenFailed ? open_panic(d.msg) : e;
         }
       };
-      const unsigned nt = (unsigned)std::min<size_t>(ctx->tree_readers, cnt);
+      const unsigned nt = (unsigned)std::min<size_t>((unsigned)ctx->opt.tree_readers, cnt);
       std::vector<std::thread> th;
       for (unsigned t = 1; t < nt; ++t) th.emplace_back(work);
       work();
@@ -3878,7 +3313,7 @@ static int tree_verify_impl(lsmck_ctx* const* ctxs, size_t nctx, const char* bas
     ~Lister() { finish(); }
   } lister;
   {
-    const unsigned lthreads = ctx->tree_list_threads ? ctx->tree_list_threads : kListThreads;
+    const unsigned lthreads = (unsigned)ctx->opt.tree_list_threads ? (unsigned)ctx->opt.tree_list_threads : kListThreads;
     for (unsigned t = 0; t < lthreads; ++t)
       lister.th.emplace_back([&lister]() {
         for (;;) {
@@ -3918,7 +3353,7 @@ static int tree_verify_impl(lsmck_ctx* const* ctxs, size_t nctx, const char* bas
   }
   // read_dir of one level: its metadata names, in batches to the parsers;
   // hook(batches published so far) after each full batch
-  const size_t list_batch = ctx->tree_list_batch ? ctx->tree_list_batch : 1024u;
+  const size_t list_batch = (size_t)ctx->opt.tree_list_batch ? (size_t)ctx->opt.tree_list_batch : 1024u;
   auto scan = [&](int lv, const std::function<void(size_t)>& hook) -> int {
     const std::string dir = lsmck_host::path_push(base, "level-" + std::to_string(lv));
     DIR* d = opendir(dir.c_str());
@@ -4008,7 +3443,7 @@ static int tree_verify_impl(lsmck_ctx* const* ctxs, size_t nctx, const char* bas
     prewarm.t.emplace_back([c = ctxs[0]]() {
       struct rlimit rl;
       if (getrlimit(RLIMIT_NOFILE, &rl) != 0 || rl.rlim_cur == RLIM_INFINITY) return;
-      const uint32_t active = c->tree_active ? c->tree_active : kTreeActive;
+      const uint32_t active = (uint32_t)c->opt.tree_active_files ? (uint32_t)c->opt.tree_active_files : kTreeActive;
       const uint64_t want = std::min<uint64_t>((uint64_t)rl.rlim_cur - 1, (uint64_t)active + 512u);
       const int fd = open("/dev/null", O_RDONLY | O_CLOEXEC);
       if (fd < 0) return;
@@ -4018,23 +3453,23 @@ static int tree_verify_impl(lsmck_ctx* const* ctxs, size_t nctx, const char* bas
     });
     for (size_t k = 0; k < nctx; ++k)
       prewarm.t.emplace_back([c = ctxs[k], n = tables]() {
-        const uint32_t active = c->tree_active ? c->tree_active : kTreeActive;
-        const uint32_t slice = c->tree_slice ? c->tree_slice : kTreeSlice;
+        const uint32_t active = (uint32_t)c->opt.tree_active_files ? (uint32_t)c->opt.tree_active_files : kTreeActive;
+        const uint32_t slice = (uint32_t)c->opt.tree_slice_bytes ? (uint32_t)c->opt.tree_slice_bytes : kTreeSlice;
         const size_t files = std::min<size_t>(active, 2 * n);
         const size_t bytes = files * ((size_t)slice + 16) + 16;  // slices are 16-B aligned in the slot
         std::lock_guard<std::mutex> lk(c->mu);
         DevGuard g(c->dev);
         for (auto& S : c->stage) {
-          if (stage_init(S) || ensure_pinned(c->pin_node, &S.h_pay, &S.cap_h_pay, bytes, true) ||
-              ensure_pinned(c->pin_node, &S.h_slices, &S.cap_h_slices, files, true) ||
-              ensure_dev(&S.d_pay, &S.cap_d_pay, bytes) || ensure_dev(&S.d_slices, &S.cap_d_slices, files))
+          if (stage_init(S) || S.h_pay.ensure(bytes, c->pin_node, true) ||
+              S.h_slices.ensure(files, c->pin_node, true) ||
+              S.d_pay.ensure(bytes) || S.d_slices.ensure(files))
             return;  // the verify reports it
           // map the pinned pages now, not on the readers' first touch
-          if (madvise(S.h_pay, S.cap_h_pay, 23 /* MADV_POPULATE_WRITE */) != 0)
-            for (size_t o = 0; o < S.cap_h_pay; o += 4096) ((volatile uint8_t*)S.h_pay)[o] = 0;
+          if (madvise(S.h_pay, S.h_pay.cap(), 23 /* MADV_POPULATE_WRITE */) != 0)
+            for (size_t o = 0; o < S.h_pay.cap(); o += 4096) ((volatile uint8_t*)S.h_pay)[o] = 0;
         }
-        (void)ensure_dev(&c->tree.state, &c->tree.cap_state, 8ull * active);
-        (void)ensure_dev(&c->tree.digests, &c->tree.cap_digests, 32 * 2 * n);
+        (void)c->tree.state.ensure(8ull * active);
+        (void)c->tree.digests.ensure(32 * 2 * n);
       });
   };
   // The top level in two parts: its first 8 x tree_overlap tables (16k by
@@ -4043,7 +3478,7 @@ static int tree_verify_impl(lsmck_ctx* const* ctxs, size_t nctx, const char* bas
   // level with fewer tables is one part, started once read).  Each part runs
   // verify_tables_multi on its own thread; their GPU halves take the
   // context in turn.
-  const size_t early_tables = 8u * (size_t)std::max<long>(ctx->tree_overlap, 1);
+  const size_t early_tables = 8u * (size_t)std::max<long>(ctx->opt.tree_overlap, 1);
   const int top = LSMCK_SSTABLE_MAX_LEVEL - 1;
   struct TopPart {
     std::vector<ListBatch*> batches;
@@ -4089,7 +3524,7 @@ static int tree_verify_impl(lsmck_ctx* const* ctxs, size_t nctx, const char* bas
       run_part(&P->part);
     });
   };
-  const bool overlap = ctx->tree_overlap > 0;
+  const bool overlap = ctx->opt.tree_overlap > 0;
   bool early = false;
   size_t ka = 0;  // top-level batches in the first part
   if ((rc = scan(top, [&](size_t nb) {
@@ -4110,7 +3545,7 @@ static int tree_verify_impl(lsmck_ctx* const* ctxs, size_t nctx, const char* bas
   for (size_t k = 0; k < top_batches; ++k) n_top += lister.batches[k]->path.size();
   if (early) {
     if (top_batches > ka) start_top(&tb, ka, top_batches, false);
-  } else if (overlap && n_top >= (size_t)ctx->tree_overlap) {
+  } else if (overlap && n_top >= (size_t)ctx->opt.tree_overlap) {
     early = true;
     ka = top_batches;
     start_top(&ta, 0, top_batches, true);
