@@ -42,6 +42,7 @@
 #endif
 
 #include "lsmck_device.h"
+#include "lsmck_splan.h"
 
 namespace lsmck {
 
@@ -1159,16 +1160,19 @@ __device__ __forceinline__ uint32_t stream_capture(const unsigned char* smem, ui
 // next lane (lane 63 loads it).  The slices' cuts follow by binary search
 // (stream_cuts, sorted by then).  One record per thread ran 0.18 ms on config
 // 3; a fused check + cuts pass 0.31 ms.
-// cut w, w = 0..W: the first record starting at or after off[0] + span*w/W
-// (cut W = n: every record belongs to exactly one wave).  Binary search.
-__device__ __forceinline__ void stream_cut(const CrcParams& P, uint32_t w, uint32_t W) {
+// cut w, w = 0..S: the first record starting at or after off[0] + span *
+// fraction(w) of the slice plan (lsmck_splan.h; cut S = n: every record
+// belongs to exactly one slice).  Binary search.  (Interior cuts rounded to
+// multiples of 64 records, for whole 256-byte output blocks, ran 0.03-0.07 ms
+// slower on config 3: the byte balance of the small slices suffers.  Not kept.)
+__device__ __forceinline__ void stream_cut(const CrcParams& P, uint32_t w, uint32_t S, uint32_t W) {
   const uint64_t n = P.nrec;
-  if (w == W) {
+  if (w == S) {
     P.scuts[w] = n;
     return;
   }
   const uint64_t o0 = P.off[0], dend = P.off[n - 1] + P.len[n - 1];
-  const uint64_t target = o0 + (dend - o0) * w / W;
+  const uint64_t target = o0 + (uint64_t)((double)(dend - o0) * splan::fraction(w, S, W));
   uint64_t a = 0, b = n;
   while (a < b) {
     const uint64_t m = (a + b) >> 1;
@@ -1182,11 +1186,11 @@ __device__ __forceinline__ void stream_cut(const CrcParams& P, uint32_t w, uint3
 // instead of a launch of their own behind it (the cuts of an ineligible batch
 // are never read: the stream kernel exits on the flag).
 template <bool VEC>
-__global__ __launch_bounds__(256) void stream_check(CrcParams P, uint32_t W) {
+__global__ __launch_bounds__(256) void stream_check(CrcParams P, uint32_t S, uint32_t W) {
   const uint64_t n = P.nrec;
   const uint32_t gt = blockIdx.x * 256u + threadIdx.x;
   if (gt == 0u) P.sflag[1] = 0u;  // the stream kernel's slice tickets
-  if (gt <= W) stream_cut(P, gt, W);
+  if (gt <= S) stream_cut(P, gt, S, W);
   const uint64_t i0 = (uint64_t)gt * 4u;  // (threads past the records load record n-1 and find nothing)
   uint64_t o[5];
   uint32_t l[5];
@@ -1223,25 +1227,29 @@ __global__ __launch_bounds__(256) void stream_check(CrcParams P, uint32_t W) {
 }
 
 // the cuts alone (trusted batches: no check)
-__global__ __launch_bounds__(256) void stream_cuts(CrcParams P, uint32_t W) {
+__global__ __launch_bounds__(256) void stream_cuts(CrcParams P, uint32_t S, uint32_t W) {
   const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
   if (w == 0u) P.sflag[1] = 0u;  // the stream kernel's slice tickets
-  if (w > W || !*P.sflag) return;
-  stream_cut(P, w, W);
+  if (w > S || !*P.sflag) return;
+  stream_cut(P, w, S, W);
 }
 
 // the tile's 64 chunks: bytes [tb, tb + 8192) from P.base (tb >= -127, the
 // chunk grid is 128-byte aligned in memory); the buffer range ends in the
-// dword holding the batch's last byte, so loads past it read zeros and touch
-// nothing
+// dword holding the slice's last byte (end4), so loads past it read zeros and
+// touch nothing: the tile at a cut is not read again by the slice before
+// (c0, a slice's first tile: the chunks in front of the first record's chunk
+// c0 belong to the slice before and are not fetched -- their lanes take an
+// offset past the range and read zeros, which reach no result: the window
+// holds no record of theirs and the first start resets its chain)
 template <int ABLATE>
 __device__ __forceinline__ void stream_issue(const CrcParams& P, int64_t tb, uintptr_t end4, uint32_t lane,
-                                             uint32_t (&u)[32]) {
+                                             uint32_t (&u)[32], uint32_t c0 = 0u) {
   const uintptr_t t0 = (uintptr_t)P.base + (uintptr_t)tb;
   const uint64_t span = end4 - t0;
   const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<unsigned char*>(P.base + tb), (short)0, (int)(span < 0x7FFFFFFFull ? span : 0x7FFFFFFFull), 0x00020000);
-  const uint32_t vo = lane * 128u;
+  const uint32_t vo = lane >= c0 ? lane * 128u : 0x80000000u;
   if (ABLATE == 2 || ABLATE == 4 || ABLATE == 10 || ABLATE == 11) {  // diagnostic: compute only (no payload loads; results invalid)
 #pragma unroll
     for (int j = 0; j < 32; ++j) u[j] = (uint32_t)tb * 0x9E3779B1u + lane + j;
@@ -1367,13 +1375,12 @@ __global__ __launch_bounds__(1024) void crc32_stream_kernel(CrcParams P) {
   const uint32_t lo = (lane & 31u) * 4u, hi = lo | 0x10000u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
   const uint64_t n = P.nrec;
-  const uint64_t dend = P.off[n - 1] + P.len[n - 1];
-  const uintptr_t end4 = ((uintptr_t)P.base + dend + 3u) & ~(uintptr_t)3;
   // chunk grid origin, relative to P.base (128-byte aligned in memory)
   const int64_t a0 = (int64_t)((((uintptr_t)P.base + P.off[0]) & ~(uintptr_t)127) - (uintptr_t)P.base);
-  // The batch is cut into P.nslice slices of equal bytes (stream_cut), several
-  // per wave on a large batch.  A wave takes slice `wave` first and then the
-  // next slice nobody has taken (a ticket counter behind the flag), until none
+  // The batch is cut into P.nslice slices (stream_cut, by the plan of
+  // lsmck_splan.h: a large first slice per wave, then groups of shrinking
+  // ones), several per wave on a large batch.  A wave takes slice `wave`
+  // first and then the next slice nobody has taken (a ticket counter behind the flag), until none
   // is left: the waves of a CU finish a launch up to 3 ms apart when each owns
   // one fixed share (tools/wave_tail.py), with the same tile counts -- the
   // SIMD's issue arbitration, not the work, decides -- and a wave that is done
@@ -1387,7 +1394,17 @@ __global__ __launch_bounds__(1024) void crc32_stream_kernel(CrcParams P) {
   asm volatile("" : "+s"(ka));
   const uint32_t nslice = ka->nslice, nwaves = ka->nwaves;
   if (slice >= nslice) break;
-  const uint64_t r_lo = ka->scuts[slice], r_hi = ka->scuts[slice + 1];
+  // The slice's records, where its first starts and where its last ends:
+  // wave-uniform by construction, and said so explicitly -- a load through a
+  // pointer that was itself loaded counts as divergent, and a buffer resource
+  // built from such a value is formed in a per-lane loop around every load
+  // (the slice's end held that way in the payload's range: 26.4-26.7 ms
+  // against 17.1, profiles/r08/handover/ab_c3_parts.log).
+  auto uni64 = [](uint64_t v) -> uint64_t {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) |
+           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  };
+  const uint64_t r_lo = uni64(ka->scuts[slice]), r_hi = uni64(ka->scuts[slice + 1]);
   if (nslice > nwaves) {  // the next slice's ticket (a batch of one slice per wave takes none)
     uint32_t tk = 0;
     if (lane == 0u) tk = atomicAdd(ka->sflag + 1, 1u);
@@ -1396,8 +1413,12 @@ __global__ __launch_bounds__(1024) void crc32_stream_kernel(CrcParams P) {
     slice = nslice;
   }
   if (r_lo >= r_hi) continue;  // no record in this slice
-  const uint64_t t_first = (uint64_t)((int64_t)P.off[r_lo] - a0) >> 13;
-  const uint64_t t_last = (uint64_t)((int64_t)(P.off[r_hi - 1] + P.len[r_hi - 1]) - a0) >> 13;
+  const uint64_t o_lo = uni64(P.off[r_lo]), e_hi = uni64(P.off[r_hi - 1] + P.len[r_hi - 1]);
+  const uint64_t t_first = (uint64_t)((int64_t)o_lo - a0) >> 13;
+  const uint64_t t_last = (uint64_t)((int64_t)e_hi - a0) >> 13;
+  const uint32_t c_first = (uint32_t)((uint64_t)((int64_t)o_lo - a0) >> 7) & 63u;  // the first record's chunk in its tile
+  // the payload's range ends in the dword holding the slice's last byte
+  const uintptr_t end4 = ((uintptr_t)P.base + e_hi + 3u) & ~(uintptr_t)3;
   // (a batch that is not sorted never gets here; the clamp keeps the loop
   // bounded whatever the descriptors hold)
   const uint64_t ntile = t_last >= t_first ? t_last - t_first + 1u : 0u;
@@ -1721,7 +1742,7 @@ __global__ __launch_bounds__(1024) void crc32_stream_kernel(CrcParams P) {
   auto none = [] {};
   uint32_t U0[32], U1[32];
   uint64_t i = 0;
-  stream_issue<ABLATE>(P, tcl(0), end4, lane, U0);
+  stream_issue<ABLATE>(P, tcl(0), end4, lane, U0, c_first);
   for (; i + 2 <= ntile; i += 2) {
     process(U0, t_first + i, [&] { stream_issue<ABLATE>(P, tcl(i + 1), end4, lane, U1); });
     process(U1, t_first + i + 1, [&] { stream_issue<ABLATE>(P, tcl(i + 2), end4, lane, U0); });
@@ -1779,19 +1800,11 @@ extern "C" int lsmk_launch_crc32_fixed(const CrcParams* P, int ncu, int variant,
   return launch_fixed<false, false>(P, ncu, st);
 }
 
-// Slices of a stream batch: one per wave (16 waves per CU), and on a batch of
-// at least 64 records per slice STREAM_SLICES per wave, which the waves take
-// one after the other (crc32_stream_kernel).  A slice costs its wave a
-// restart -- the window, a first tile that is not prefetched, the tile at the
-// cut read by both neighbours -- so it is kept at tens of tiles or more.
-#ifndef STREAM_SLICES
-#define STREAM_SLICES 16u
-#endif
-extern "C" uint32_t lsmk_stream_slices_max(int ncu) { return (uint32_t)ncu * 16u * STREAM_SLICES; }
-static uint32_t stream_slices(int ncu, uint64_t n) {
-  const uint64_t w = (uint64_t)ncu * 16u;
-  return (uint32_t)std::min<uint64_t>(w * STREAM_SLICES, std::max<uint64_t>(w, n / 64u));
-}
+// Slices of a stream batch and where their cuts lie: lsmck_splan.h.  A slice
+// costs its wave a restart -- the window, a first tile that is not
+// prefetched, the tile at the cut read by both neighbours -- so the smallest
+// is kept at tens of tiles.
+extern "C" uint32_t lsmk_stream_slices_max(int ncu) { return splan::slices_max(ncu); }
 
 // whether this library carries the stream kernel's diagnostic ablations (crc_ablate 2, 4..10)
 extern "C" int lsmk_ab_ablations() {
@@ -1811,15 +1824,15 @@ extern "C" int lsmk_launch_crc32_stream(const CrcParams* P, int ncu, int variant
   if (n == 0) return 0;
   hipError_t e = hipMemsetAsync(P->sflag, 1, 4, st);
   if (e != hipSuccess) return -(int)e;
-  const uint32_t W = stream_slices(ncu, n);
+  const uint32_t W = splan::slices(ncu, n), NW = splan::waves(ncu);
   if (!trusted) {  // a caller's batch: checked first, the cuts computed inside the check
     const bool vec = ((uintptr_t)P->off % 16u == 0) && ((uintptr_t)P->len % 16u == 0);
     const uint64_t nb = std::max<uint64_t>((n + 1023) / 1024, (W + 1u + 255u) / 256u);
     const dim3 g((unsigned)nb);
-    if (vec) hipLaunchKernelGGL(stream_check<true>, g, dim3(256), 0, st, *P, W);
-    else hipLaunchKernelGGL(stream_check<false>, g, dim3(256), 0, st, *P, W);
+    if (vec) hipLaunchKernelGGL(stream_check<true>, g, dim3(256), 0, st, *P, W, NW);
+    else hipLaunchKernelGGL(stream_check<false>, g, dim3(256), 0, st, *P, W, NW);
   } else {
-    hipLaunchKernelGGL(stream_cuts, dim3((W + 1u + 255u) / 256u), dim3(256), 0, st, *P, W);
+    hipLaunchKernelGGL(stream_cuts, dim3((W + 1u + 255u) / 256u), dim3(256), 0, st, *P, W, NW);
   }
   const int ablate = (variant >> 8) & 0xF;
 #ifdef LSMCK_AB_ABLATIONS
@@ -1846,7 +1859,7 @@ extern "C" int lsmk_launch_crc32_stream(const CrcParams* P, int ncu, int variant
   if (e != hipSuccess) return -(int)e;
   CrcParams Q = *P;
   Q.nslice = W;
-  Q.nwaves = (uint32_t)ncu * 16u;
+  Q.nwaves = NW;
   void* args[] = {(void*)&Q};
   e = hipLaunchKernel(fn, dim3(ncu), dim3(1024), args, lds, st);
   if (e != hipSuccess) return -(int)e;
