@@ -44,7 +44,7 @@ extern "C" {
 #define LSMCK_ENOMEM (-12)
 #define LSMCK_EIO (-5)
 #define LSMCK_ENODEV (-19)
-#define LSMCK_ENOSPC (-28) /* lsmck_wal_encode_batch, lsmck_sstable_encode_batch: an output buffer is too small */
+#define LSMCK_ENOSPC (-28) /* the batch builders (encode, build, decode, merge): an output buffer is too small */
 #define LSMCK_EHIP (-1000) /* LSMCK_EHIP - hipError_t */
 
 /* flags for batch calls */
@@ -282,7 +282,9 @@ int lsmck_device_count(void);
  *   "sst_encode_time"  DIAGNOSTIC, not part of the stable option list, as
  *                 "wal_encode_time": 1 = lsmck_sstable_encode_batch records
  *                 device events around its stages (tools/sst_encode_big.py
- *                 reads them back as stats); 0 = none (default).
+ *                 reads them back as stats); 0 = none (default).  It times
+ *                 lsmck_sstable_decode_batch and lsmck_sstable_merge_batch
+ *                 the same way (tools/merge_big.py).
  *   "mem_build_time"  DIAGNOSTIC, not part of the stable option list, as
  *                 "wal_encode_time": 1 = lsmck_memtable_build records device
  *                 events around its stages (tools/memtable_big.py reads them
@@ -320,6 +322,23 @@ int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value);
  *                    stages between device events, with "sst_encode_time" 1:
  *                    sizes / order / index plan / spans, the data gather, the
  *                    index writer, the two digest passes.
+ *   "sst_decode_declined"  the tables of the last lsmck_sstable_decode_batch
+ *                    whose index file was given and refused as a hint (they
+ *                    were walked by one lane; the entries are the same).
+ *   "sst_decode_uniform"  ... whose index file holds keys of one length: its
+ *                    items lie a fixed step apart and were proven in place by
+ *                    a thread each, without the serial parse.
+ *   "sst_decode_index_ns", "sst_decode_seg_ns", "sst_decode_scan_ns",
+ *   "sst_decode_emit_ns"  DIAGNOSTIC, subject to change: the last
+ *                    lsmck_sstable_decode_batch's stages, with
+ *                    "sst_encode_time" 1: the index walk, the segment walks,
+ *                    the counts (plain walks included) and their scan, the
+ *                    entries.
+ *   "sst_merge_okey_ns", "sst_merge_shadow_ns", "sst_merge_scan_ns",
+ *   "sst_merge_place_ns"  DIAGNOSTIC, subject to change: the last
+ *                    lsmck_sstable_merge_batch's stages, with
+ *                    "sst_encode_time" 1: validation and order keys, shadow,
+ *                    the scan, place.
  *   "mem_rounds"     the chunk rounds the last lsmck_memtable_build ran (0 for
  *                    fewer than two commands; each round is a host round trip).
  *   "mem_validate_ns", "mem_chunk_ns", "mem_sort_ns", "mem_resolve_ns"
@@ -638,6 +657,119 @@ int lsmck_memtable_build(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes,
  * 0, a negative hipError_t code, or LSMCK_ENODEV without a GPU. */
 int lsmck_wal_recs_to_cmds(lsmck_ctx* ctx, const lsmck_wal_rec16* recs, size_t n, uint64_t img_bytes,
                            lsmck_wal_cmd* cmds, void* stream);
+
+/* Batch SSTable decode: the batch form of the data file's iterator
+ * (src/sync/sstable.rs:77-90 over datafile.rs:60-83) -- the inverse of
+ * lsmck_sstable_encode_batch, and the first step of a compaction on the
+ * device (decode, lsmck_sstable_merge_batch, lsmck_sstable_encode_batch).
+ * Table t's data file is data[spans[t].data_off .. + data_len) (the encode's
+ * own span type; the tables may lie anywhere in the arena).  Its entries are
+ * exactly the records the reference's iterator yields: from pos = 0, u32 klen
+ * LE, u32 vlen LE, the key, the value; UnexpectedEof anywhere (a header cut
+ * after 0..7 bytes, a key cut, a value cut) ends the table cleanly and the
+ * partial record is dropped; pos advances by 8 + klen + vlen.  They are
+ * written to ents[0 .. *nent), table after table, as lsmck_wal_cmd of type 1,
+ * reserved 0, key_off and val_off pointing into `data`: the caller later
+ * passes keys = vals = data.  tab_first (always a HOST pointer, ntab + 1
+ * values) receives the tables' first entry numbers -- the table_first of the
+ * merge and of the encode.  consumed (optional, ntab values) receives the
+ * bytes each table's iterator got through, so that a caller can see a cut
+ * tail (consumed[t] < data_len).  decode(encode(x)) == x entry for entry.
+ * `index` (may be NULL) holds the tables' index files at spans[t].index_off /
+ * index_len.  The chain of headers is serial inside a table: without an index
+ * one GPU lane walks a table.  With one, the index -- the position of every
+ * 100th record (sstable_index.rs:42-46) -- is a hint that is proven before it
+ * is used: a thread per 100 records walks the headers from an item's position
+ * and must land on the next item's.  The hint is taken for a table only if its
+ * image parses to exactly index_len, pos_0 == 0, the positions increase inside
+ * data_len, every segment passes exactly 100 records and lands on the next
+ * position (an index whose keys have one length is parsed by a thread per
+ * item: an item found in its expected place with that length proves the next
+ * one's place), the last one ends after 1..100 records where the next record no
+ * longer fits (an empty table: a count of 0 and no whole record).  Any other
+ * table is walked by one lane (stat "sst_decode_declined" counts them).  The
+ * entries never depend on the index: merge_compact does not read it.
+ * flags: LSMCK_DEVICE -- data, index, spans, ents and consumed are device
+ * pointers; LSMCK_HOST (optionally | LSMCK_HOST_PINNED, a hint only) -- host
+ * pointers, staged whole.  Any other flag bit is LSMCK_EINVAL.  tab_first,
+ * nent and bad_index are host pointers either way.  Synchronous; the total
+ * and the error word are read back once, before anything is written.
+ * Returns 0, or
+ *   LSMCK_EINVAL  with *bad_index = the first table whose data span (or, with
+ *                 an index, index span) lies outside its arena, or whose
+ *                 data_len is above 2^32-1 (under that limit a record that
+ *                 fits cannot wrap the reference's u32 8 + klen + vlen,
+ *                 datafile.rs:81); with *bad_index = UINT64_MAX: an argument.
+ *   LSMCK_ENOSPC  cap < *nent: *nent is the count needed.
+ *   LSMCK_ENODEV  there is no GPU (and so no context).
+ * On any error no byte of ents, tab_first or consumed is written. */
+int lsmck_sstable_decode_batch(lsmck_ctx* ctx, const uint8_t* data, size_t data_bytes, const uint8_t* index,
+                               size_t index_bytes, const lsmck_sstable_span* spans, size_t ntab, lsmck_wal_cmd* ents,
+                               size_t cap, uint64_t* tab_first, uint64_t* consumed, size_t* nent, uint64_t* bad_index,
+                               unsigned flags);
+
+/* Host helper, no GPU, scalar: the records the reference's iterator yields
+ * from the data file image img[0 .. n) (the walk above on the calling
+ * thread); *consumed (optional) = the bytes it got through.  For callers that
+ * size buffers.  Sizes are formed in 64 bits. */
+uint64_t lsmck_sstable_count_records(const uint8_t* img, size_t n, uint64_t* consumed);
+
+/* Batch compaction merge: the batch form of SsTable::merge_compact's loop
+ * (src/sync/sstable.rs:151-224, src/tokio/sstable.rs:135-207; driven by
+ * compact, sync/lsm_storage.rs:141-157) over sorted runs of entries -- the
+ * decode's output, or any strictly increasing run: a memtable build's output
+ * is a valid table.  Entries, arenas and tab_first as in
+ * lsmck_sstable_encode_batch (tab_first: HOST, ntab + 1 entry numbers).
+ * Group g merges tables [group_first[g], group_first[g + 1]) (group_first:
+ * HOST, ngrp + 1 table numbers), oldest first, as in the reference's vector:
+ * the loop scans the tables in vector order, `<=` moves the choice to the
+ * later table on equal keys and the earlier table's equal entry is advanced
+ * past (:171-189), so every distinct key comes out once, in Vec<u8> order
+ * (bytewise, unsigned, a proper prefix first), taken from the
+ * highest-numbered table of the group that holds it.  out[0 .. *nout)
+ * receives the winners in key order, group after group, their ranges still
+ * pointing into the caller's arenas; src (optional) the winner's index in
+ * ents; out_first (HOST, ngrp + 1) the groups' first output entries -- the
+ * table_first for lsmck_sstable_encode_batch.  Empty tables and empty groups
+ * are allowed.
+ * Tombstones (a winner whose value is the one byte 0): the reference's loop
+ * does `continue` without advancing anything (:193-195) and never terminates.
+ * By default the call returns LSMCK_MERGE_STUCK with *bad_index = the first
+ * such winner in (group, key) order -- where the reference stops making
+ * progress -- and writes nothing.  With LSMCK_MERGE_DROP_TOMBSTONES the key
+ * leaves the output (what the reference's line plainly means to do); with
+ * LSMCK_MERGE_KEEP_TOMBSTONES it stays as an ordinary pair (a merge above the
+ * bottom level needs that to keep shadowing lower levels).  Both flags
+ * together are LSMCK_EINVAL.  A tombstone that a newer table shadows is
+ * harmless in every mode.
+ * On the device (lsmck_sstmerge.hip, lsmck_sstmerge.h) the runs are not
+ * sorted again: an entry is shadowed when a lower bound finds its key in a
+ * newer table of its group; the live flags are scanned; a live entry's slot
+ * is its group's base plus, over the group's tables, the live prefix at the
+ * lower bound of its key.
+ * flags: LSMCK_DEVICE -- keys, vals, ents (8-byte aligned), out and src are
+ * device pointers; LSMCK_HOST (optionally | LSMCK_HOST_PINNED, a hint only)
+ * -- host pointers, staged whole.  Synchronous; the count and the error
+ * words are read back once, before anything is written.
+ * Returns 0, LSMCK_MERGE_STUCK, or
+ *   LSMCK_EINVAL  with *bad_index = the first offending entry: it fails
+ *                 lsmck_sstable_encode_batch's entry rule (type, record size,
+ *                 source ranges), or it is not the first of its table and
+ *                 its key is not strictly greater than its predecessor's.
+ *                 With *bad_index = UINT64_MAX (checked before any GPU
+ *                 work): tab_first or group_first is malformed, n, ntab or
+ *                 ngrp is 2^32 or more, an unknown flag or both tombstone
+ *                 flags.
+ *   LSMCK_ENOSPC  cap < *nout: *nout is the count needed.
+ *   LSMCK_ENODEV  there is no GPU (and so no context).
+ * On any error no byte of out, src or out_first is written. */
+#define LSMCK_MERGE_STUCK 7
+#define LSMCK_MERGE_DROP_TOMBSTONES 0x100u
+#define LSMCK_MERGE_KEEP_TOMBSTONES 0x200u
+int lsmck_sstable_merge_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes, const uint8_t* vals,
+                              size_t vals_bytes, const lsmck_wal_cmd* ents, size_t n, const uint64_t* tab_first,
+                              size_t ntab, const uint64_t* group_first, size_t ngrp, lsmck_wal_cmd* out, size_t cap,
+                              uint32_t* src, uint64_t* out_first, size_t* nout, uint64_t* bad_index, unsigned flags);
 
 /* Whole-tree SSTable verify: the batch form of Checksums::verify over many
  * tables (Db::load, src/tokio/db.rs:37-59 -> src/tokio/sstable.rs:34).

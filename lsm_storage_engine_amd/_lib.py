@@ -35,6 +35,7 @@ META_PANIC = 3  # lsmck_tree_verify status: metadata file unreadable / not SsTab
 PANIC_OPEN_FILE = 4      # checksums.rs:25 "Can't open file to calculate checksum" (the data file in verify/write)
 PANIC_OPEN_INDEX = 5     # the same panic on the index file
 PANIC_OPEN_CHECKSUM = 6  # checksums.rs:46 "Can't open checksum file"
+MERGE_STUCK = 7  # lsmck_sstable_merge_batch: a tombstone wins its key (the reference's loop never terminates there)
 SSTABLE_MAX_LEVEL = 5
 
 DEVICE = 0x1
@@ -43,6 +44,8 @@ HOST_PINNED = 0x2
 SORTED = 0x4  # LSMCK_SORTED: device descriptors sorted inside one readable span (include/lsmck.h)
 RECS_PINNED = 0x8  # LSMCK_RECS_PINNED: lsmck_wal_replay_verify's records array is page-locked
 RECS_DEVICE = 0x10  # LSMCK_RECS_DEVICE: the records array is device memory (include/lsmck.h)
+MERGE_DROP_TOMBSTONES = 0x100  # lsmck_sstable_merge_batch: a tombstone winner leaves the output
+MERGE_KEEP_TOMBSTONES = 0x200  # ... stays as an ordinary pair
 
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
@@ -148,6 +151,11 @@ SIGNATURES = [
     ("lsmck_memtable_build", C.c_int,  # cmds: lsmck_wal_cmd[n]; ents: lsmck_wal_cmd[cap]; src: u32[cap]
      [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, C.POINTER(sz), u64p, u64p, C.c_uint]),
     ("lsmck_wal_recs_to_cmds", C.c_int, [vp, vp, sz, C.c_uint64, vp, vp]),  # recs: lsmck_wal_rec16[n]
+    ("lsmck_sstable_decode_batch", C.c_int,  # spans: lsmck_sstable_span[ntab]; tab_first: host u64[ntab + 1]
+     [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(sz), u64p, C.c_uint]),
+    ("lsmck_sstable_count_records", C.c_uint64, [vp, sz, u64p]),
+    ("lsmck_sstable_merge_batch", C.c_int,  # tab_first, group_first, out_first: host u64 arrays
+     [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(sz), u64p, C.c_uint]),
     ("lsmck_checksums_verify_many", C.c_int,
      [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), sz, C.POINTER(C.c_int)]),
     ("lsmck_tree_verify", C.c_int, [vp, C.c_char_p, C.POINTER(TreeReport)]),

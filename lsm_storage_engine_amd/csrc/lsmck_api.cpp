@@ -44,6 +44,7 @@
 #include "lsmck_options.h"
 #include "lsmck_pool.h"
 #include "lsmck_segwalk.h"
+#include "lsmck_sstmerge.h"
 
 using lsmck::CrcParams;
 using lsmck::ShaParams;
@@ -422,6 +423,38 @@ struct lsmck_ctx {
   } mem;
   StageTimer mem_timer;  // "mem_build_time": validate, mem_chunk, the rounds' fixed-width part, resolve / emit
   long mem_rounds = 0;   // the last build's rounds
+  // batch SSTable decode (lsmck_device.h DecArgs): the per-table and
+  // per-segment scratch, the call's four words and their pinned copy; host
+  // form: both images, the spans and the entries
+  struct {
+    DevBuf<uint64_t> segfirst, segpos, cons, tabfirst, bsum;
+    DevBuf<uint32_t> state, fail, lastcnt;
+    DevBuf<uint8_t> hint;
+    DevBuf<unsigned long long> info;
+    PinBuf<unsigned long long> h_info;
+    DevBuf<uint8_t> data, index;
+    DevBuf<lsmck_sstable_span> spans;
+    DevBuf<lsmck_wal_cmd> ents;
+  } dec;
+  StageTimer dec_timer;   // "sst_encode_time" (this call too): index walk, segment walks, counts / plain walks / scan, emit
+  long dec_declined = 0;  // the last decode's tables whose index was refused
+  long dec_uniform = 0;   // ... whose index was proven item by item (keys of one length)
+  // batch merge (lsmck_device.h MrgArgs): per entry the order key, the table,
+  // the live flag / its scan and the tombstone flag; table_first, group_first
+  // and every table's group on the device; the groups' first outputs; the
+  // call's three words and their pinned copy; host form: the winners and
+  // their sources
+  struct {
+    DevBuf<lsmck::mrg::OKey> ok;
+    DevBuf<uint32_t> etab, tgrp;
+    DevBuf<uint64_t> tf, gf, live, gout, bsum;
+    DevBuf<uint8_t> tomb;
+    DevBuf<unsigned long long> info;
+    PinBuf<unsigned long long> h_info;
+    DevBuf<lsmck_wal_cmd> out;
+    DevBuf<uint32_t> src;
+  } mrg;
+  StageTimer mrg_timer;  // "sst_encode_time" (this call too): order keys / validation, shadow, scan, place
   bool wal_recs_direct = false;  // this replay's records go by DMA into the caller's pinned array (under wal_mu)
   bool wal_compact = false;      // this replay's records are lsmck_wal_rec16 (under wal_mu)
   // LSMCK_RECS_DEVICE (under wal_mu): the caller's device array and its capacity
@@ -1003,6 +1036,26 @@ int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value) {
     *value = ctx->sst_timer.ns[3];
   } else if (!strcmp(key, "mem_rounds")) {  // the last lsmck_memtable_build's chunk rounds
     *value = ctx->mem_rounds;
+  } else if (!strcmp(key, "sst_decode_declined")) {  // the last lsmck_sstable_decode_batch's refused indexes
+    *value = ctx->dec_declined;
+  } else if (!strcmp(key, "sst_decode_uniform")) {  // ... whose index was proven item by item, in parallel
+    *value = ctx->dec_uniform;
+  } else if (!strcmp(key, "sst_decode_index_ns")) {  // the last timed decode's stages ("sst_encode_time")
+    *value = ctx->dec_timer.ns[0];
+  } else if (!strcmp(key, "sst_decode_seg_ns")) {
+    *value = ctx->dec_timer.ns[1];
+  } else if (!strcmp(key, "sst_decode_scan_ns")) {
+    *value = ctx->dec_timer.ns[2];
+  } else if (!strcmp(key, "sst_decode_emit_ns")) {
+    *value = ctx->dec_timer.ns[3];
+  } else if (!strcmp(key, "sst_merge_okey_ns")) {  // the last timed merge's stages ("sst_encode_time")
+    *value = ctx->mrg_timer.ns[0];
+  } else if (!strcmp(key, "sst_merge_shadow_ns")) {
+    *value = ctx->mrg_timer.ns[1];
+  } else if (!strcmp(key, "sst_merge_scan_ns")) {
+    *value = ctx->mrg_timer.ns[2];
+  } else if (!strcmp(key, "sst_merge_place_ns")) {
+    *value = ctx->mrg_timer.ns[3];
   } else if (!strcmp(key, "mem_validate_ns")) {  // the last timed build's stages ("mem_build_time")
     *value = ctx->mem_timer.ns[0];
   } else if (!strcmp(key, "mem_chunk_ns")) {
@@ -2471,6 +2524,205 @@ int lsmck_wal_recs_to_cmds(lsmck_ctx* ctx, const lsmck_wal_rec16* recs, size_t n
   if (!recs || !cmds) return lsmck_host::set_error(LSMCK_EINVAL, "null records or commands");
   DevGuard g(ctx->dev);
   return launch_rc(lsmk_mem_recs_to_cmds(recs, n, img_bytes, cmds, pick_stream(ctx, stream)), "wal_recs_to_cmds kernel");
+}
+
+int lsmck_sstable_decode_batch(lsmck_ctx* ctx, const uint8_t* data, size_t data_bytes, const uint8_t* index,
+                               size_t index_bytes, const lsmck_sstable_span* spans, size_t ntab, lsmck_wal_cmd* ents,
+                               size_t cap, uint64_t* tab_first, uint64_t* consumed, size_t* nent, uint64_t* bad_index,
+                               unsigned flags) {
+  if (nent) *nent = 0;
+  if (bad_index) *bad_index = ~0ull;
+  if (!nent || !tab_first) return lsmck_host::set_error(LSMCK_EINVAL, "sstable decode: null nent or tab_first");
+  if (flags & ~(LSMCK_DEVICE | LSMCK_HOST_PINNED))
+    return lsmck_host::set_error(LSMCK_EINVAL, "sstable decode: unknown flag");
+  if (ntab >= (1ull << 32))
+    return lsmck_host::set_error(LSMCK_EINVAL, "sstable decode: more than 2^32-1 tables in one batch");
+  if (!ctx) return mem_no_ctx("sstable decode");
+  if (ntab == 0) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->dec_declined = ctx->dec_uniform = 0;
+    tab_first[0] = 0;
+    return 0;
+  }
+  if (!spans || (data_bytes && !data)) return lsmck_host::set_error(LSMCK_EINVAL, "sstable decode: null spans or data");
+  if (!index) index_bytes = 0;
+  int rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DevGuard g(ctx->dev);
+  const hipStream_t st = ctx->stream0;
+  ScratchOrder so(ctx, st);
+  if (so.e != hipSuccess) return hip_error(so.e, "hipStreamWaitEvent(scratch)");
+  auto& D = ctx->dec;
+  const bool dev = (flags & LSMCK_DEVICE) != 0;
+  lsmck::DecArgs A{};
+  A.data = data, A.index = index, A.spans = spans;
+  if (!dev) {  // the host form is staged whole
+    if ((rc = D.data.ensure(data_bytes)) || (rc = D.index.ensure(index_bytes)) || (rc = D.spans.ensure(ntab))) return rc;
+    if (data_bytes) HIPCHK(hipMemcpyAsync(D.data, data, data_bytes, hipMemcpyHostToDevice, st));
+    if (index_bytes) HIPCHK(hipMemcpyAsync(D.index, index, index_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(D.spans, spans, ntab * sizeof(lsmck_sstable_span), hipMemcpyHostToDevice, st));
+    A.data = D.data, A.index = index ? D.index.get() : nullptr, A.spans = D.spans;
+  }
+  A.data_bytes = data_bytes, A.index_bytes = index_bytes, A.ntab = ntab;
+  // an index item is 16 bytes or more: the segments' scratch is sized without a read-back
+  A.nslots = index ? index_bytes / 16 + ntab : 0;
+  if ((rc = D.segfirst.ensure(ntab + 1)) || (rc = D.segpos.ensure((size_t)A.nslots)) || (rc = D.cons.ensure(ntab)) ||
+      (rc = D.tabfirst.ensure(ntab + 1)) || (rc = D.bsum.ensure((size_t)lsmk_sst_scan_blocks(ntab) + 1)) ||
+      (rc = D.state.ensure(ntab)) || (rc = D.fail.ensure(ntab)) || (rc = D.lastcnt.ensure(ntab)) ||
+      (rc = D.hint.ensure(ntab)) || (rc = D.info.ensure(5)) || (rc = D.h_info.ensure(5, -1)))
+    return rc;
+  A.segfirst = D.segfirst, A.segpos = D.segpos, A.cons = D.cons, A.tabfirst = D.tabfirst, A.bsum = D.bsum;
+  A.state = D.state, A.fail = D.fail, A.lastcnt = D.lastcnt, A.hint = D.hint, A.info = D.info;
+  HIPCHK(hipMemsetAsync(A.info, 0xFF, 8, st));
+  HIPCHK(hipMemsetAsync(A.info + 1, 0, 32, st));
+  StageTimer& T = ctx->dec_timer;
+  T.begin(ctx->opt.sst_encode_time);
+  // 1.-4. the hint, its check, the counts; the total and the error word come back once
+  HIPCHK(T.mark(0, st));
+  if ((rc = lsmk_dec_index(&A, st))) return launch_rc(rc, "sstable decode index kernels");
+  HIPCHK(T.mark(1, st));
+  if ((rc = lsmk_dec_segments(&A, st))) return launch_rc(rc, "sstable decode segment kernel");
+  HIPCHK(T.mark(2, st));
+  if ((rc = lsmk_dec_count(&A, st))) return launch_rc(rc, "sstable decode count / scan kernels");
+  HIPCHK(T.mark(3, st));
+  HIPCHK(hipMemcpyAsync(D.h_info, A.info, 40, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const uint64_t bad = D.h_info[0], total = D.h_info[1];
+  if (bad != ~0ull) {
+    if (bad_index) *bad_index = bad;
+    return lsmck_host::set_error(LSMCK_EINVAL,
+                                 "sstable decode: a table's span lies outside its arena, or its data file is above "
+                                 "2^32-1 bytes");
+  }
+  ctx->dec_declined = (long)D.h_info[2];
+  ctx->dec_uniform = (long)D.h_info[4];
+  *nent = (size_t)total;
+  if (cap < total) return lsmck_host::set_error(LSMCK_ENOSPC, "sstable decode: cap is smaller than the entries");
+  if (total && !ents) return lsmck_host::set_error(LSMCK_EINVAL, "null ents");
+  lsmck_wal_cmd* de = ents;
+  if (!dev && total) {
+    if ((rc = D.ents.ensure((size_t)total))) return rc;
+    de = D.ents;
+  }
+  // 5. the entries
+  if (total && (rc = lsmk_dec_emit(&A, de, st))) return launch_rc(rc, "sstable decode emit kernels");
+  HIPCHK(T.mark(4, st));
+  HIPCHK(hipMemcpyAsync(tab_first, A.tabfirst, (ntab + 1) * 8, hipMemcpyDeviceToHost, st));
+  if (consumed)
+    HIPCHK(hipMemcpyAsync(consumed, A.cons, ntab * 8, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  if (!dev && total)
+    HIPCHK(hipMemcpyAsync(ents, de, (size_t)total * sizeof(lsmck_wal_cmd), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int k = 0; k < 4; ++k) HIPCHK(T.span(k, k + 1, k));
+  T.finish();
+  return 0;
+}
+
+int lsmck_sstable_merge_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes, const uint8_t* vals,
+                              size_t vals_bytes, const lsmck_wal_cmd* ents, size_t n, const uint64_t* tab_first,
+                              size_t ntab, const uint64_t* group_first, size_t ngrp, lsmck_wal_cmd* out, size_t cap,
+                              uint32_t* src, uint64_t* out_first, size_t* nout, uint64_t* bad_index, unsigned flags) {
+  if (nout) *nout = 0;
+  if (bad_index) *bad_index = ~0ull;
+  if (!nout || !out_first) return lsmck_host::set_error(LSMCK_EINVAL, "sstable merge: null nout or out_first");
+  const unsigned modes = LSMCK_MERGE_DROP_TOMBSTONES | LSMCK_MERGE_KEEP_TOMBSTONES;
+  if (flags & ~(LSMCK_DEVICE | LSMCK_HOST_PINNED | modes))
+    return lsmck_host::set_error(LSMCK_EINVAL, "sstable merge: unknown flag");
+  if ((flags & modes) == modes)
+    return lsmck_host::set_error(LSMCK_EINVAL, "sstable merge: both tombstone flags are set");
+  if (n >= (1ull << 32) || ntab >= (1ull << 32) || ngrp >= (1ull << 32))
+    return lsmck_host::set_error(LSMCK_EINVAL, "sstable merge: more than 2^32-1 entries, tables or groups in one batch");
+  // table_first and group_first, on the host, before any GPU work
+  if (!tab_first || !group_first) return lsmck_host::set_error(LSMCK_EINVAL, "sstable merge: null tab_first or group_first");
+  if (tab_first[0] != 0 || tab_first[ntab] != n)
+    return lsmck_host::set_error(LSMCK_EINVAL, "sstable merge: tab_first must start at 0 and end at n");
+  for (size_t t = 0; t < ntab; ++t)
+    if (tab_first[t + 1] < tab_first[t]) return lsmck_host::set_error(LSMCK_EINVAL, "sstable merge: tab_first decreases");
+  if (group_first[0] != 0 || group_first[ngrp] != ntab)
+    return lsmck_host::set_error(LSMCK_EINVAL, "sstable merge: group_first must start at 0 and end at ntab");
+  for (size_t q = 0; q < ngrp; ++q)
+    if (group_first[q + 1] < group_first[q])
+      return lsmck_host::set_error(LSMCK_EINVAL, "sstable merge: group_first decreases");
+  if (!ctx) return mem_no_ctx("sstable merge");
+  if (n == 0) {
+    for (size_t q = 0; q <= ngrp; ++q) out_first[q] = 0;
+    return 0;
+  }
+  if (!ents) return lsmck_host::set_error(LSMCK_EINVAL, "null entries");
+  std::vector<uint32_t> tgrp(ntab);
+  for (size_t q = 0; q < ngrp; ++q)
+    for (uint64_t t = group_first[q]; t < group_first[q + 1]; ++t) tgrp[(size_t)t] = (uint32_t)q;
+  int rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DevGuard g(ctx->dev);
+  const hipStream_t st = ctx->stream0;
+  ScratchOrder so(ctx, st);
+  if (so.e != hipSuccess) return hip_error(so.e, "hipStreamWaitEvent(scratch)");
+  auto& M = ctx->mrg;
+  const bool dev = (flags & LSMCK_DEVICE) != 0;
+  const uint8_t *dk = keys, *dv = vals;
+  const lsmck_wal_cmd* dc = ents;
+  if (!dev && (rc = stage_inputs(ctx, &dk, keys_bytes, &dv, vals_bytes, true, &dc, n, st))) return rc;
+  if ((rc = M.ok.ensure(n)) || (rc = M.etab.ensure(n)) || (rc = M.tgrp.ensure(ntab)) || (rc = M.tf.ensure(ntab + 1)) ||
+      (rc = M.gf.ensure(ngrp + 1)) || (rc = M.live.ensure(n + 1)) || (rc = M.gout.ensure(ngrp + 1)) ||
+      (rc = M.bsum.ensure((size_t)lsmk_sst_scan_blocks(n) + 1)) || (rc = M.tomb.ensure(n)) ||
+      (rc = M.info.ensure(3)) || (rc = M.h_info.ensure(3, -1)))
+    return rc;
+  HIPCHK(hipMemcpyAsync(M.tf, tab_first, (ntab + 1) * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(M.gf, group_first, (ngrp + 1) * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(M.tgrp, tgrp.data(), ntab * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(M.info, 0xFF, 24, st));
+  lsmck::MrgArgs A{};
+  A.keys = dk, A.vals = dv, A.keys_bytes = keys_bytes, A.vals_bytes = vals_bytes, A.ents = dc;
+  A.n = n, A.ntab = ntab, A.ngrp = ngrp, A.tf = M.tf, A.gf = M.gf, A.tgrp = M.tgrp, A.ok = M.ok, A.etab = M.etab;
+  A.live = M.live, A.gout = M.gout, A.bsum = M.bsum, A.tomb = M.tomb, A.info = M.info;
+  A.mode = (flags & LSMCK_MERGE_DROP_TOMBSTONES) ? 1u : (flags & LSMCK_MERGE_KEEP_TOMBSTONES) ? 2u : 0u;
+  StageTimer& T = ctx->mrg_timer;
+  T.begin(ctx->opt.sst_encode_time);
+  // 1.-3. validity and order keys, shadow, the scan; the count and the error words come back once
+  HIPCHK(T.mark(0, st));
+  if ((rc = lsmk_mrg_keys(&A, st))) return launch_rc(rc, "sstable merge order key kernels");
+  HIPCHK(T.mark(1, st));
+  if ((rc = lsmk_mrg_shadow(&A, st))) return launch_rc(rc, "sstable merge shadow kernel");
+  HIPCHK(T.mark(2, st));
+  if ((rc = lsmk_mrg_scan(&A, st))) return launch_rc(rc, "sstable merge scan kernels");
+  HIPCHK(T.mark(3, st));
+  HIPCHK(hipMemcpyAsync(M.h_info, M.info, 24, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const uint64_t bad = M.h_info[0], total = M.h_info[1], stuck = M.h_info[2];
+  if (bad != ~0ull) {
+    if (bad_index) *bad_index = bad;
+    return lsmck_host::set_error(LSMCK_EINVAL,
+                                 "sstable merge: invalid entry (type, lengths, source range or key order inside its table)");
+  }
+  if (stuck != ~0ull) {
+    if (bad_index) *bad_index = stuck & 0xFFFFFFFFull;
+    return lsmck_host::set_error(LSMCK_MERGE_STUCK,
+                                 "sstable merge: a tombstone wins its key: the reference's loop stops advancing there "
+                                 "(sstable.rs:193-195); pass LSMCK_MERGE_DROP_TOMBSTONES or LSMCK_MERGE_KEEP_TOMBSTONES");
+  }
+  *nout = (size_t)total;
+  if (cap < total) return lsmck_host::set_error(LSMCK_ENOSPC, "sstable merge: cap is smaller than the winners");
+  if (total && !out) return lsmck_host::set_error(LSMCK_EINVAL, "null out");
+  lsmck_wal_cmd* dout = out;
+  uint32_t* ds = src;
+  if (!dev && total) {
+    if ((rc = M.out.ensure((size_t)total)) || (src && (rc = M.src.ensure((size_t)total)))) return rc;
+    dout = M.out;
+    ds = src ? M.src.get() : nullptr;
+  }
+  // 4. place
+  if (total && (rc = lsmk_mrg_place(&A, dout, ds, st))) return launch_rc(rc, "sstable merge place kernel");
+  HIPCHK(T.mark(4, st));
+  HIPCHK(hipMemcpyAsync(out_first, M.gout, (ngrp + 1) * 8, hipMemcpyDeviceToHost, st));
+  if (!dev && total) {
+    HIPCHK(hipMemcpyAsync(out, dout, (size_t)total * sizeof(lsmck_wal_cmd), hipMemcpyDeviceToHost, st));
+    if (src) HIPCHK(hipMemcpyAsync(src, ds, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  for (int k = 0; k < 4; ++k) HIPCHK(T.span(k, k + 1, k));
+  T.finish();
+  return 0;
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@
 
 #include "lsmck.h"
 #include "lsmck_internal.h"
+#include "lsmck_sstmerge.h"
 
 #if defined(__x86_64__)
 #include <cpuid.h>
@@ -482,6 +483,13 @@ int lsmck_sstable_encoded_size(const lsmck_wal_cmd* ents, size_t n, const uint64
   if (data_bytes) *data_bytes = data;
   if (index_bytes) *index_bytes = index;
   return 0;
+}
+
+uint64_t lsmck_sstable_count_records(const uint8_t* img, size_t n, uint64_t* consumed) {
+  uint64_t end = 0;
+  const uint64_t c = n ? lsmck::mrg::walk(img, n, 0, 0, ~0ull, nullptr, &end) : 0;
+  if (consumed) *consumed = end;
+  return c;
 }
 
 void lsmck_gen_zipf_lengths(uint64_t seed, double s, int kmax, uint32_t lmin, size_t n, uint32_t* out) {

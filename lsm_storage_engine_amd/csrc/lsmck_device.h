@@ -80,9 +80,64 @@ struct MemWs {
   uint8_t *tail, *head;
 };
 
+// The batch SSTable decode's arguments and scratch (lsmck_sstmerge.hip dec_*).
+// Per table: segfirst (its hint's items, then their exclusive scan: its place
+// in segpos; ntab + 1), state / fail (lsmck_sstmerge.hip kDec*; bit 0 of fail:
+// a segment's landing did not check, bit 1: its spans were refused), lastcnt
+// (its last segment's records), cons (the bytes its iterator got through),
+// tabfirst (its entries, then their exclusive scan; ntab + 1), hint (its
+// entries come from the segments).  segpos: nslots segment starts.  info: 5
+// words -- [0] the first table refused (atomic min, set to ~0 by the caller),
+// [1] the entries, [2] the tables whose index was refused (set to 0), [3] the
+// segments, [4] the tables whose index was proven item by item (set to 0).
+namespace mrg { struct OKey; }
+struct DecArgs {
+  const uint8_t *data, *index;  // index: null without a hint
+  uint64_t data_bytes, index_bytes;
+  const lsmck_sstable_span* spans;
+  uint64_t ntab, nslots;
+  uint64_t *segfirst, *segpos, *cons, *tabfirst, *bsum;
+  uint32_t *state, *fail, *lastcnt;
+  uint8_t* hint;
+  unsigned long long* info;
+};
+// The batch merge's (mrg_*).  Per entry: ok (its order key), etab (its
+// table), live (its live flag, then the flags' exclusive scan; n + 1), tomb
+// (a tombstone winner to report).  tf / gf: table_first and group_first on
+// the device; tgrp: every table's group; gout: the groups' first output
+// entries (ngrp + 1).  mode: 0 report tombstone winners, 1 drop them, 2 keep
+// them.  info: 3 words set to ~0 by the caller -- [0] the first entry refused
+// (atomic min), [1] the live entries, [2] the first tombstone winner (its
+// output slot << 32 | the entry; atomic min).
+struct MrgArgs {
+  const uint8_t *keys, *vals;
+  uint64_t keys_bytes, vals_bytes;
+  const lsmck_wal_cmd* ents;
+  uint64_t n, ntab, ngrp;
+  const uint64_t *tf, *gf;
+  const uint32_t* tgrp;
+  mrg::OKey* ok;
+  uint32_t* etab;
+  uint64_t *live, *gout, *bsum;
+  uint8_t* tomb;
+  uint32_t mode;
+  unsigned long long* info;
+};
+
 }  // namespace lsmck
 
 extern "C" {
+// batch SSTable decode and merge (lsmck_sstmerge.hip); ntab > 0 and n > 0
+int lsmk_dec_index(const lsmck::DecArgs* a, hipStream_t st);     // spans, index parse, segment starts
+int lsmk_dec_segments(const lsmck::DecArgs* a, hipStream_t st);  // the segments' check
+int lsmk_dec_count(const lsmck::DecArgs* a, hipStream_t st);     // counts (plain walks) and their scan
+int lsmk_dec_emit(const lsmck::DecArgs* a, lsmck_wal_cmd* ents, hipStream_t st);
+int lsmk_mrg_keys(const lsmck::MrgArgs* a, hipStream_t st);    // validity, order keys, tables, key order
+int lsmk_mrg_shadow(const lsmck::MrgArgs* a, hipStream_t st);  // live flags
+int lsmk_mrg_scan(const lsmck::MrgArgs* a, hipStream_t st);    // their scan, the stuck word, the groups' firsts
+int lsmk_mrg_place(const lsmck::MrgArgs* a, lsmck_wal_cmd* out, uint32_t* src, hipStream_t st);
+// exclusive scan of v[0..n) in place, v[n] and *total = the sum (bsum: lsmk_sst_scan_blocks(n) + 1 entries)
+int lsmk_sst_scan(uint64_t* v, uint64_t n, uint64_t* bsum, unsigned long long* total, hipStream_t st);
 // batch memtable build (lsmck_memtable_build; lsmck_memtable.hip mem_*)
 size_t lsmk_mem_carve(uint8_t* ws, uint64_t n, lsmck::MemWs* W);
 int lsmk_mem_validate(const lsmck_wal_cmd* cmds, uint64_t n, uint64_t keys_bytes, uint64_t vals_bytes,

@@ -252,6 +252,9 @@ static int sst_scan(uint64_t* v, uint64_t n, uint64_t* bsum, unsigned long long*
   hipLaunchKernelGGL(sst_scan_c, dim3(nb), dim3(SST_SCAN_BLOCK), 0, st, v, n, (const uint64_t*)bsum, total);
   return sst_launch_err();
 }
+extern "C" int lsmk_sst_scan(uint64_t* v, uint64_t n, uint64_t* bsum, unsigned long long* total, hipStream_t st) {
+  return sst_scan(v, n, bsum, total, st);
+}
 extern "C" int lsmk_sst_sizes(const lsmck_wal_cmd* ents, uint64_t n, uint64_t keys_bytes, uint64_t vals_bytes,
                               uint64_t* off, uint64_t* bsum, unsigned long long* info, hipStream_t st) {
   if (n) hipLaunchKernelGGL(sst_size, dim3(sst_grid(n)), dim3(256), 0, st, ents, n, keys_bytes, vals_bytes, off, info);

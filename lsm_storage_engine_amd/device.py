@@ -126,6 +126,33 @@ class MemBuildError(_lib.LsmckError):
         super().__init__(rc, f"{what} (bad_index={bad_index}, needed={needed})")
 
 
+class SstDecodeError(_lib.LsmckError):
+    """lsmck_sstable_decode_batch refused the batch: ``bad_index`` is the first
+    table whose span is refused (LSMCK_EINVAL; None for an argument error), or
+    ``needed`` the entries' count when the array given holds fewer
+    (LSMCK_ENOSPC); the other one is None."""
+
+    def __init__(self, rc, what, bad_index=None, needed=None):
+        self.bad_index = bad_index
+        self.needed = needed
+        super().__init__(rc, f"{what} (bad_index={bad_index}, needed={needed})")
+
+
+class SstMergeError(_lib.LsmckError):
+    """lsmck_sstable_merge_batch refused the batch: ``bad_index`` is the first
+    offending entry (LSMCK_EINVAL; None for an argument error) or, with
+    ``stuck`` set, the first tombstone winner in (group, key) order
+    (LSMCK_MERGE_STUCK: the reference's loop never terminates there);
+    ``needed`` the winners' count when the array given holds fewer
+    (LSMCK_ENOSPC)."""
+
+    def __init__(self, rc, what, bad_index=None, needed=None, stuck=False):
+        self.bad_index = bad_index
+        self.needed = needed
+        self.stuck = stuck
+        super().__init__(rc, f"{what} (bad_index={bad_index}, needed={needed}, stuck={stuck})")
+
+
 class Context:
     def __init__(self, device=0):
         lib = _lib.load()
@@ -436,6 +463,107 @@ class Context:
         nothing was written then."""
         return self._mem_build(keys_ptr, keys_bytes, vals_ptr, vals_bytes, cmds_ptr, n, ents_ptr, cap, src_ptr,
                                _lib.DEVICE)
+
+    def _sst_decode(self, data, db, index, ib, spans, ntab, ents, cap, consumed, flags):
+        none = 2 ** 64 - 1
+        tf = np.zeros(ntab + 1, dtype=np.uint64)
+        nent, bad = C.c_size_t(), C.c_uint64(none)
+        rc = self.lib.lsmck_sstable_decode_batch(self.handle, data, db, index, ib, spans, ntab, ents, cap,
+                                                 tf.ctypes.data, consumed, C.byref(nent), C.byref(bad), flags)
+        if rc == _lib.EINVAL:
+            raise SstDecodeError(rc, "sstable_decode_batch", bad_index=None if bad.value == none else bad.value)
+        if rc == _lib.ENOSPC:
+            raise SstDecodeError(rc, "sstable_decode_batch", needed=nent.value)
+        _lib.check(rc, "sstable_decode_batch")
+        return nent.value, tf
+
+    def sstable_decode_batch(self, data, spans, index=None, pinned=False):
+        """lsmck_sstable_decode_batch, host form: the entries of the tables
+        whose data files lie in the uint8 arena ``data`` at ``spans``
+        (SSTABLE_SPAN_DTYPE; ``index``: the arena of their index files, or
+        None), walked on the GPU as the reference's iterator walks them.
+        Returns (ents: WAL_CMD_DTYPE, key_off / val_off into ``data``;
+        tab_first: np.uint64, ntab + 1; consumed: np.uint64 per table).
+        Raises SstDecodeError (``bad_index``: the first table refused)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        index = None if index is None else np.ascontiguousarray(index, dtype=np.uint8)
+        spans = np.ascontiguousarray(spans, dtype=_lib.SSTABLE_SPAN_DTYPE)
+        ntab = len(spans)
+        ents = np.empty(data.nbytes // 8, dtype=_lib.WAL_CMD_DTYPE)  # (a record is 8 bytes or more)
+        consumed = np.zeros(ntab, dtype=np.uint64)
+        flags = _lib.HOST_PINNED if pinned else _lib.HOST
+        try:
+            nent, tf = self._sst_decode(data.ctypes.data, data.nbytes, _p(index), 0 if index is None else index.nbytes,
+                                        spans.ctypes.data, ntab, ents.ctypes.data, len(ents), consumed.ctypes.data,
+                                        flags)
+        except SstDecodeError as e:
+            if e.needed is None:
+                raise
+            ents = np.empty(e.needed, dtype=_lib.WAL_CMD_DTYPE)  # (overlapping spans: more entries than bytes / 8)
+            nent, tf = self._sst_decode(data.ctypes.data, data.nbytes, _p(index), 0 if index is None else index.nbytes,
+                                        spans.ctypes.data, ntab, ents.ctypes.data, len(ents), consumed.ctypes.data,
+                                        flags)
+        return ents[:nent], tf, consumed
+
+    def sstable_decode_batch_device(self, data_ptr, data_bytes, index_ptr, index_bytes, spans_ptr, ntab, ents_ptr, cap,
+                                    consumed_ptr=None):
+        """lsmck_sstable_decode_batch on device pointers (spans: ntab
+        lsmck_sstable_span; index_ptr: None without a hint; ents: cap
+        lsmck_wal_cmd; consumed_ptr: ntab u64 or None).  Returns (nent,
+        tab_first: a host np.uint64 array of ntab + 1); raises SstDecodeError
+        with ``bad_index`` or ``needed``; nothing was written then."""
+        return self._sst_decode(data_ptr, data_bytes, index_ptr, index_bytes, spans_ptr, ntab, ents_ptr, cap,
+                                consumed_ptr, _lib.DEVICE)
+
+    def _sst_merge(self, keys, kb, vals, vb, ents, n, tab_first, group_first, out, cap, src, flags, tombstones):
+        none = 2 ** 64 - 1
+        mode = {"stuck": 0, "drop": _lib.MERGE_DROP_TOMBSTONES, "keep": _lib.MERGE_KEEP_TOMBSTONES}[tombstones]
+        tf = np.ascontiguousarray(tab_first, dtype=np.uint64)
+        gf = np.ascontiguousarray(group_first, dtype=np.uint64)
+        if len(tf) < 1 or len(gf) < 1:
+            raise ValueError("tab_first holds ntab + 1 values, group_first ngrp + 1")
+        of = np.zeros(len(gf), dtype=np.uint64)
+        nout, bad = C.c_size_t(), C.c_uint64(none)
+        rc = self.lib.lsmck_sstable_merge_batch(self.handle, keys, kb, vals, vb, ents, n, tf.ctypes.data, len(tf) - 1,
+                                                gf.ctypes.data, len(gf) - 1, out, cap, src, of.ctypes.data,
+                                                C.byref(nout), C.byref(bad), flags | mode)
+        if rc == _lib.MERGE_STUCK:
+            raise SstMergeError(rc, "sstable_merge_batch", bad_index=bad.value, stuck=True)
+        if rc == _lib.EINVAL:
+            raise SstMergeError(rc, "sstable_merge_batch", bad_index=None if bad.value == none else bad.value)
+        if rc == _lib.ENOSPC:
+            raise SstMergeError(rc, "sstable_merge_batch", needed=nout.value)
+        _lib.check(rc, "sstable_merge_batch")
+        return nout.value, of
+
+    def sstable_merge_batch(self, keys, vals, ents, tab_first, group_first, tombstones="stuck", pinned=False):
+        """lsmck_sstable_merge_batch, host form: the sorted tables that
+        ``tab_first`` cuts ``ents`` into, merged group by group
+        (``group_first``: ngrp + 1 table numbers; oldest table first, the
+        newest wins a key) on the GPU.  ``tombstones``: "stuck" (a tombstone
+        winner raises SstMergeError with ``stuck``), "drop" or "keep".
+        Returns (out: WAL_CMD_DTYPE, the winners in key order, group after
+        group; src: np.uint32, their indices in ``ents``; out_first:
+        np.uint64, ngrp + 1)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint8)
+        vals = keys if vals is keys else np.ascontiguousarray(vals, dtype=np.uint8)
+        ents = np.ascontiguousarray(ents, dtype=_lib.WAL_CMD_DTYPE)
+        n = len(ents)
+        out = np.empty(n, dtype=_lib.WAL_CMD_DTYPE)  # (at most every entry wins)
+        src = np.empty(n, dtype=np.uint32)
+        flags = _lib.HOST_PINNED if pinned else _lib.HOST
+        nout, of = self._sst_merge(keys.ctypes.data, keys.nbytes, vals.ctypes.data, vals.nbytes, ents.ctypes.data, n,
+                                   tab_first, group_first, out.ctypes.data, n, src.ctypes.data, flags, tombstones)
+        return out[:nout], src[:nout], of
+
+    def sstable_merge_batch_device(self, keys_ptr, keys_bytes, vals_ptr, vals_bytes, ents_ptr, n, tab_first,
+                                   group_first, out_ptr, cap, src_ptr=None, tombstones="stuck"):
+        """lsmck_sstable_merge_batch on device pointers (ents: n lsmck_wal_cmd;
+        tab_first, group_first: host arrays; out: cap lsmck_wal_cmd; src_ptr:
+        cap u32 or None).  Returns (nout, out_first: a host np.uint64 array of
+        ngrp + 1); raises SstMergeError; nothing was written then."""
+        return self._sst_merge(keys_ptr, keys_bytes, vals_ptr, vals_bytes, ents_ptr, n, tab_first, group_first, out_ptr,
+                               cap, src_ptr, _lib.DEVICE, tombstones)
 
     def wal_recs_to_cmds_device(self, recs_ptr, n, img_bytes, cmds_ptr, stream=None):
         """lsmck_wal_recs_to_cmds: n compact replay records (lsmck_wal_rec16,

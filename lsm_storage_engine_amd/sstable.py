@@ -173,4 +173,176 @@ def flush_log_image(base_path, image, ctx, timestamp_ms=None):
             b.free()
 
 
-__all__ = ["from_memtable", "flush_many", "flush_log_image", "table_bytes", "batch_arrays", "INDEX_STEP"]
+class MergeStuck(RuntimeError):
+    """merge_compact met a tombstone (value ``[0]``) that wins its key: the
+    reference's loop does ``continue`` there without advancing anything
+    (src/sync/sstable.rs:193-195) and never terminates.  ``key`` is that key."""
+
+    def __init__(self, key):
+        self.key = bytes(key)
+        super().__init__(f"merge_compact: the tombstone of key {self.key!r} wins; the reference's loop never "
+                         f"terminates there (tombstones='drop' or 'keep' chooses a meaning)")
+
+
+def iter_records(image):
+    """The reference's iterator over a data file image (sync/sstable.rs:77-90,
+    datafile.rs:60-83): (key, value) pairs from pos 0; UnexpectedEof anywhere
+    -- the header, the key or the value cut -- ends the table cleanly."""
+    image = bytes(image)
+    pos = 0
+    while len(image) - pos >= 8:
+        klen, vlen = struct.unpack_from("<II", image, pos)
+        if len(image) - pos - 8 < klen + vlen:
+            return
+        yield image[pos + 8:pos + 8 + klen], image[pos + 8 + klen:pos + 8 + klen + vlen]
+        pos += (8 + klen + vlen) & 0xFFFFFFFF  # (u32, datafile.rs:81; a record that fits a file under 4 GiB cannot wrap)
+
+
+def read_table(meta):
+    """The (key, value) pairs the reference's iterator yields from the table's data file."""
+    with open(meta.data_path(), "rb") as f:
+        return iter_records(f.read())
+
+
+def merge_loop(tables, tombstones="stuck"):
+    """SsTable::merge_compact's loop (sync/sstable.rs:157-208), literally, over
+    tables given as iterables of (key, value) in the reference's vector order
+    (oldest first).  A tombstone winner raises MergeStuck ("stuck": the
+    reference never terminates), is advanced past ("drop") or written
+    ("keep").  Returns the pairs written, in order."""
+    if tombstones not in ("stuck", "drop", "keep"):
+        raise ValueError(tombstones)
+    iterators = [iter(t) for t in tables]
+    values = [next(it, None) for it in iterators]
+    out = []
+    while True:
+        current = None
+        for i in range(len(iterators)):
+            kv = values[i]
+            if kv is None:
+                continue
+            if current is None:
+                current = i
+            else:
+                curr = current
+                if kv[0] <= values[curr][0]:
+                    current = i
+                if values[curr][0] == kv[0]:
+                    values[curr] = next(iterators[curr], None)
+        if current is None:
+            return out
+        kv = values[current]
+        if kv[1] == b"\x00":
+            if tombstones == "stuck":
+                raise MergeStuck(kv[0])
+            if tombstones == "drop":
+                values[current] = next(iterators[current], None)
+                continue
+        out.append(kv)
+        values[current] = next(iterators[current], None)
+
+
+def merge_compact_many(base_path, jobs, ctx, tombstones="stuck"):
+    """Many compactions in one pass over the device: ``jobs`` is a list of
+    (level, tables) or (level, tables, timestamp_ms), ``tables`` the
+    SsTableMetadata of one merge in the reference's order (oldest first).  The
+    old tables' data and index files are uploaded once; decode
+    (lsmck_sstable_decode_batch, the index files as the proven hint), merge
+    (lsmck_sstable_merge_batch, one group per job) and encode
+    (lsmck_sstable_encode_batch) run on the device in one context, and only the
+    new data files, index files and digests come back.  Removing the old
+    tables stays with the caller.  Returns the new tables' SsTableMetadata."""
+    from .device import SstEncodeError, SstMergeError
+    jobs = [tuple(j) if len(j) == 3 else (j[0], j[1], None) for j in jobs]
+    if not jobs:
+        return []
+    t0 = int(time.time() * 1000)
+    metas = [SsTableMetadata.new(str(base_path), level, timestamp_ms=t0 + i if ts is None else ts)
+             for i, (level, _, ts) in enumerate(jobs)]
+    old = [m for _, tables, _ in jobs for m in tables]
+    datas = [open(m.data_path(), "rb").read() for m in old]
+    idxs = [open(m.index_path(), "rb").read() for m in old]
+    spans = np.zeros(len(old), dtype=_lib.SSTABLE_SPAN_DTYPE)
+    spans["data_len"], spans["index_len"] = [len(d) for d in datas], [len(x) for x in idxs]
+    spans["data_off"] = np.cumsum(spans["data_len"]) - spans["data_len"]
+    spans["index_off"] = np.cumsum(spans["index_len"]) - spans["index_len"]
+    group_first = np.zeros(len(jobs) + 1, dtype=np.uint64)
+    group_first[1:] = np.cumsum([len(tables) for _, tables, _ in jobs])
+    arena, iarena = b"".join(datas), b"".join(idxs)
+    db, ib, ntab = len(arena), len(iarena), len(old)
+    bufs = []
+
+    def alloc(nbytes):
+        bufs.append(ctx.alloc(max(nbytes, 1)))
+        return bufs[-1]
+    try:
+        d_data, d_index, d_spans = alloc(db), alloc(ib), alloc(32 * ntab)
+        if db:
+            d_data.upload(np.frombuffer(arena, np.uint8))
+        if ib:
+            d_index.upload(np.frombuffer(iarena, np.uint8))
+        if ntab:
+            d_spans.upload(spans)
+        cap = db // 8  # (a record is 8 bytes or more, and the spans do not overlap)
+        d_ents, d_out = alloc(32 * cap), alloc(32 * cap)
+        nent, tab_first = ctx.sstable_decode_batch_device(d_data.ptr, db, d_index.ptr if ib else None, ib, d_spans.ptr,
+                                                          ntab, d_ents.ptr, cap)
+        try:
+            nout, out_first = ctx.sstable_merge_batch_device(d_data.ptr, db, d_data.ptr, db, d_ents.ptr, nent, tab_first,
+                                                             group_first, d_out.ptr, cap, tombstones=tombstones)
+        except SstMergeError as e:
+            if not e.stuck:
+                raise
+            c = d_ents.download(_lib.WAL_CMD_DTYPE, 1, 32 * e.bad_index)[0]
+            raise MergeStuck(arena[int(c["key_off"]):int(c["key_off"]) + int(c["klen"])]) from e
+        args = (d_data.ptr, db, d_data.ptr, db, d_out.ptr, nout, out_first)
+        # The encode's size query (as in flush_log_image): with no buffers at all it runs its
+        # size passes, writes nothing and reports LSMCK_ENOSPC with both sizes -- an index file
+        # holds its count at least, so this call cannot succeed.
+        try:
+            ctx.sstable_encode_batch_device(*args, None, 0, None, 0)
+            raise AssertionError("an index file is never empty")
+        except SstEncodeError as e:
+            if e.needed is None:
+                raise
+            ndb, nib = e.needed
+        ng = len(jobs)
+        n_data, n_index, n_spans, n_sha = alloc(ndb), alloc(nib), alloc(32 * ng), alloc(64 * ng)
+        got = ctx.sstable_encode_batch_device(*args, n_data.ptr, ndb, n_index.ptr, nib, n_spans.ptr, n_sha.ptr,
+                                              n_sha.ptr + 32 * ng)
+        assert got == (ndb, nib)
+        data, index = n_data.download(np.uint8, ndb), n_index.download(np.uint8, nib)
+        nspans = n_spans.download(_lib.SSTABLE_SPAN_DTYPE, ng)
+        sha = n_sha.download(np.uint8, 64 * ng).reshape(2, ng, 32)
+    finally:
+        for b in bufs:
+            b.free()
+    for g, m in enumerate(metas):
+        sp = nspans[g]
+        d0, i0 = int(sp["data_off"]), int(sp["index_off"])
+        _write_table(m, memoryview(data)[d0:d0 + int(sp["data_len"])], memoryview(index)[i0:i0 + int(sp["index_len"])],
+                     sha[1][g], sha[0][g])
+    return metas
+
+
+def merge_compact(base_path, level, tables, ctx=None, tombstones="stuck", timestamp_ms=None):
+    """SsTable::merge_compact (src/sync/sstable.rs:151-224, tokio/sstable.rs:135-207):
+    the tables (SsTableMetadata, in the reference's vector order: oldest first,
+    the newest wins a key) merged into one table of ``level``.  With a context
+    the files are uploaded once and decode, merge and encode run on the device
+    (merge_compact_many); without one the literal loop runs here (merge_loop).
+    The files are equal either way.  ``tombstones``: "stuck" raises MergeStuck
+    where the reference's loop never terminates, "drop" leaves the key out,
+    "keep" writes the tombstone.  Removing the old tables stays with the
+    caller.  Returns the new table's SsTableMetadata."""
+    if tombstones not in ("stuck", "drop", "keep"):
+        raise ValueError(tombstones)
+    if ctx is not None:
+        return merge_compact_many(base_path, [(level, tables, timestamp_ms)], ctx, tombstones)[0]
+    entries = merge_loop([read_table(m) for m in tables], tombstones)
+    m = SsTableMetadata.new(str(base_path), level, timestamp_ms=timestamp_ms)
+    return _write_table(m, *table_bytes(entries))
+
+
+__all__ = ["from_memtable", "flush_many", "flush_log_image", "table_bytes", "batch_arrays", "INDEX_STEP",
+           "iter_records", "read_table", "merge_loop", "merge_compact", "merge_compact_many", "MergeStuck"]
