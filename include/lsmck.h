@@ -284,7 +284,9 @@ int lsmck_device_count(void);
  *                 device events around its stages (tools/sst_encode_big.py
  *                 reads them back as stats); 0 = none (default).  It times
  *                 lsmck_sstable_decode_batch and lsmck_sstable_merge_batch
- *                 the same way (tools/merge_big.py).
+ *                 the same way (tools/merge_big.py), and
+ *                 lsmck_sstable_get_batch (tools/get_big.py), whose probe
+ *                 then also counts its pairs.
  *   "mem_build_time"  DIAGNOSTIC, not part of the stable option list, as
  *                 "wal_encode_time": 1 = lsmck_memtable_build records device
  *                 events around its stages (tools/memtable_big.py reads them
@@ -339,6 +341,14 @@ int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value);
  *                    lsmck_sstable_merge_batch's stages, with
  *                    "sst_encode_time" 1: validation and order keys, shadow,
  *                    the scan, place.
+ *   "sst_get_index_ns", "sst_get_probe_ns", "sst_get_resolve_ns"
+ *                    DIAGNOSTIC, subject to change: the last
+ *                    lsmck_sstable_get_batch's stages, with "sst_encode_time"
+ *                    1: the index pass, the queries' check and the probe of
+ *                    every (query, table) pair, resolve; and
+ *                    "sst_get_probed" / "sst_get_walked", the pairs that
+ *                    probe looked up (the others were skipped behind a lower
+ *                    table's answer) and those whose interval it walked.
  *   "mem_rounds"     the chunk rounds the last lsmck_memtable_build ran (0 for
  *                    fewer than two commands; each round is a host round trip).
  *   "mem_validate_ns", "mem_chunk_ns", "mem_sort_ns", "mem_resolve_ns"
@@ -770,6 +780,93 @@ int lsmck_sstable_merge_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_b
                               size_t vals_bytes, const lsmck_wal_cmd* ents, size_t n, const uint64_t* tab_first,
                               size_t ntab, const uint64_t* group_first, size_t ngrp, lsmck_wal_cmd* out, size_t cap,
                               uint32_t* src, uint64_t* out_first, size_t* nout, uint64_t* bad_index, unsigned flags);
+
+/* Batch point reads: the batch form of SsTable::get (src/sync/sstable.rs:97-113,
+ * src/tokio/sstable.rs:57-82) over the tables of Db::get_internal's loop
+ * (src/tokio/db.rs:178-185), for tables that stay device-resident (written by
+ * lsmck_sstable_encode_batch, or uploaded).  Table t's data and index files lie
+ * at spans[t] in `data` and `index` (the encode's span type).  Query i's key is
+ * qkeys[q[i].key_off .. + klen); an empty key's offset is not looked at.
+ * One key in one table, literally, quirks included:
+ *   - The index file is the bincode fixint image of BTreeMap<Vec<u8>, u64>
+ *     (sstable_index.rs:20-25).  It is taken as the map when it parses to
+ *     exactly index_len bytes and its keys strictly increase in Vec<u8> order
+ *     (bytewise, unsigned, a proper prefix first): file order is then map
+ *     order and no key repeats.  ANY OTHER INDEX IS REFUSED -- the one
+ *     deliberate refusal: the reference panics at load ("Can't open index
+ *     file") or never writes such a file.  Positions may be any u64.
+ *   - The map holds the key (sstable.rs:102-106): the result is the value of
+ *     the record at the item's position WHATEVER ITS KEY IS -- the reference
+ *     does not compare.  A position where no whole record fits gives None.
+ *   - Otherwise position_range (sstable_index.rs:34-40): start = the position
+ *     of the last item below the key, or 0; end = the position of the first
+ *     item above it, or data_len.  scan_range (datafile.rs:85-103) reads the
+ *     record at start EVEN WHEN start >= end, returns it when its key equals
+ *     the key, else advances and stops once pos >= end or no whole record
+ *     fits.  The scan is not bounded by 100 records: an index with an item
+ *     missing makes an interval of 200.
+ *   - read_record (datafile.rs:60-83): fewer than 8 bytes left, or a cut key
+ *     or value, gives None.  data_len <= 2^32-1, as for the decode.
+ *   - The bloom filter (sstable.rs:98) is not read: a filter built from the
+ *     table's own keys has no false negatives, so it never changes a result,
+ *     only the work.  The bloom file is out of scope, as everywhere here.
+ * Over tables 0..ntab-1 IN THE ORDER GIVEN (search order: the caller passes
+ * level 0 newest first, then level 1, and so on, as db.rs:178-185 iterates) a
+ * key's result comes from the first table whose get is Some.  That includes a
+ * tombstone, the one byte 0: get_internal stops there and Db::get turns it
+ * into "not found" (db.rs:146-151).  res[i] says which of the three it is:
+ *   table == LSMCK_GET_NONE           no table answered (val_off = 0, vlen = 0);
+ *   val_off & LSMCK_GET_TOMBSTONE     table `table` answered with a tombstone
+ *                                     (vlen = 1);
+ *   otherwise                         the value is data[val_off .. + vlen).
+ * Bits 0..62 of val_off hold the value's offset in `data` in every Some.
+ * On the device (lsmck_sstget.hip, lsmck_sstget.h): an index pass leaves one
+ * 16-byte order key, the offset and the position per index item (a thread per
+ * item for an index of one key length, one lane per table otherwise) and
+ * proves the key order; a work item per (query, table) pair does a lower bound
+ * over the order keys and the exact hit's read or the interval's walk of
+ * headers, and lowers the query's winning table with an atomic minimum; a
+ * thread per query repeats the lookup in the winning table and writes res.
+ * Not covered: Db::get's memtable and old-memtable step (a host dict, or a
+ * lower bound over lsmck_memtable_build's output), a resident "opened table"
+ * form that keeps the index pass between calls, and sorting queries by
+ * interval so that one walk serves many.
+ * flags: LSMCK_DEVICE -- data, index, spans, qkeys, q (8-byte aligned) and res
+ * are device pointers; LSMCK_HOST (optionally | LSMCK_HOST_PINNED, a hint
+ * only) -- host pointers, staged whole.  Any other flag bit is LSMCK_EINVAL.
+ * bad_table and bad_query are host pointers (may be NULL) and are set to
+ * UINT64_MAX unless they name something.  Synchronous; the error words are
+ * read back once, before res is written.
+ * Returns 0 (n == 0: nothing is written; ntab == 0: every result is
+ * LSMCK_GET_NONE), or
+ *   LSMCK_EINVAL  with *bad_table = the first table whose data or index span
+ *                 lies outside its arena, whose data_len is above 2^32-1, or
+ *                 whose index is refused under the rule above; else
+ *                 with *bad_query = the first query whose non-empty key lies
+ *                 outside [0, qkeys_bytes) or whose reserved != 0 (tables are
+ *                 checked before queries); else
+ *                 with both UINT64_MAX (checked before any GPU work): n or
+ *                 ntab is 2^32 or more, index is NULL while ntab > 0, a null
+ *                 array that is needed, or a wrong flag.
+ *   LSMCK_ENODEV  there is no GPU (and so no context).
+ * On any error no byte of res is written. */
+typedef struct { uint64_t key_off; uint32_t klen; uint32_t reserved; } lsmck_get_query;   /* 16 bytes */
+typedef struct { uint64_t val_off; uint32_t vlen; uint32_t table; } lsmck_get_result;     /* 16 bytes */
+#define LSMCK_GET_NONE 0xFFFFFFFFu                 /* table: no table answered (val_off = 0, vlen = 0) */
+#define LSMCK_GET_TOMBSTONE 0x8000000000000000ull  /* bit 63 of val_off: the value is the byte 0 */
+int lsmck_sstable_get_batch(lsmck_ctx* ctx, const uint8_t* data, size_t data_bytes, const uint8_t* index,
+                            size_t index_bytes, const lsmck_sstable_span* spans, size_t ntab, const uint8_t* qkeys,
+                            size_t qkeys_bytes, const lsmck_get_query* q, size_t n, lsmck_get_result* res,
+                            uint64_t* bad_table, uint64_t* bad_query, unsigned flags);
+
+/* Host helper, no GPU, scalar: SsTable::get of one key in one table (the rules
+ * above, the same code on the calling thread) -- the latency path.  Returns 1
+ * (Some: *val_off = the value's offset in `data`, *vlen its length; a
+ * tombstone is a Some of the one byte 0), 0 (None; both set to 0), or
+ * LSMCK_EINVAL: the index is refused, data_len is above 2^32-1, or val_off or
+ * vlen is NULL.  The index is parsed on every call (O(items)). */
+int lsmck_sstable_get(const uint8_t* data, size_t data_len, const uint8_t* index, size_t index_len,
+                      const uint8_t* key, uint32_t klen, uint64_t* val_off, uint32_t* vlen);
 
 /* Whole-tree SSTable verify: the batch form of Checksums::verify over many
  * tables (Db::load, src/tokio/db.rs:37-59 -> src/tokio/sstable.rs:34).

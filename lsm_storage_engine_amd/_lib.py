@@ -93,6 +93,13 @@ class SstableSpan(C.Structure):
 SSTABLE_SPAN_DTYPE = np.dtype([("data_off", "<u8"), ("data_len", "<u8"), ("index_off", "<u8"), ("index_len", "<u8")])
 assert SSTABLE_SPAN_DTYPE.itemsize == C.sizeof(SstableSpan) == 32
 
+# include/lsmck.h lsmck_get_query and lsmck_get_result (16 bytes each, no padding)
+GET_QUERY_DTYPE = np.dtype([("key_off", "<u8"), ("klen", "<u4"), ("reserved", "<u4")])
+GET_RESULT_DTYPE = np.dtype([("val_off", "<u8"), ("vlen", "<u4"), ("table", "<u4")])
+assert GET_QUERY_DTYPE.itemsize == GET_RESULT_DTYPE.itemsize == 16
+GET_NONE = 0xFFFFFFFF  # LSMCK_GET_NONE: lsmck_get_result.table when no table answered
+GET_TOMBSTONE = 1 << 63  # LSMCK_GET_TOMBSTONE: bit 63 of lsmck_get_result.val_off
+
 
 class TreeReport(C.Structure):
     _fields_ = [("tables", C.c_uint64), ("table_bytes", C.c_uint64), ("bad_tables", C.c_uint64),
@@ -156,6 +163,9 @@ SIGNATURES = [
     ("lsmck_sstable_count_records", C.c_uint64, [vp, sz, u64p]),
     ("lsmck_sstable_merge_batch", C.c_int,  # tab_first, group_first, out_first: host u64 arrays
      [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, vp, C.POINTER(sz), u64p, C.c_uint]),
+    ("lsmck_sstable_get_batch", C.c_int,  # q: lsmck_get_query[n]; res: lsmck_get_result[n]; bad_table, bad_query: host
+     [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, u64p, u64p, C.c_uint]),
+    ("lsmck_sstable_get", C.c_int, [vp, sz, vp, sz, vp, C.c_uint32, u64p, u32p]),
     ("lsmck_checksums_verify_many", C.c_int,
      [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), sz, C.POINTER(C.c_int)]),
     ("lsmck_tree_verify", C.c_int, [vp, C.c_char_p, C.POINTER(TreeReport)]),

@@ -455,6 +455,23 @@ struct lsmck_ctx {
     DevBuf<uint32_t> src;
   } mrg;
   StageTimer mrg_timer;  // "sst_encode_time" (this call too): order keys / validation, shadow, scan, place
+  // batch point read (lsmck_device.h GetArgs): the per-table, per-item and
+  // per-query scratch, the call's five words and their pinned copy; host
+  // form: the arenas, the spans, the queries and the results
+  struct {
+    DevBuf<uint64_t> itemfirst, bsum, ioff, ipos;
+    DevBuf<lsmck::mrg::OKey> iok, qok;
+    DevBuf<uint32_t> state, fail, win;
+    DevBuf<unsigned long long> info;
+    PinBuf<unsigned long long> h_info;
+    DevBuf<uint8_t> data, index, qkeys;
+    DevBuf<lsmck_sstable_span> spans;
+    DevBuf<lsmck_get_query> q;
+    DevBuf<lsmck_get_result> res;
+  } get;
+  StageTimer get_timer;  // "sst_encode_time" (this call too): index pass, queries / probe, resolve
+  long get_probed = 0;   // the last timed read's (query, table) pairs looked up
+  long get_walked = 0;   // ... whose interval was walked
   bool wal_recs_direct = false;  // this replay's records go by DMA into the caller's pinned array (under wal_mu)
   bool wal_compact = false;      // this replay's records are lsmck_wal_rec16 (under wal_mu)
   // LSMCK_RECS_DEVICE (under wal_mu): the caller's device array and its capacity
@@ -1056,6 +1073,16 @@ int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value) {
     *value = ctx->mrg_timer.ns[2];
   } else if (!strcmp(key, "sst_merge_place_ns")) {
     *value = ctx->mrg_timer.ns[3];
+  } else if (!strcmp(key, "sst_get_index_ns")) {  // the last timed point read's stages ("sst_encode_time")
+    *value = ctx->get_timer.ns[0];
+  } else if (!strcmp(key, "sst_get_probe_ns")) {
+    *value = ctx->get_timer.ns[1];
+  } else if (!strcmp(key, "sst_get_resolve_ns")) {
+    *value = ctx->get_timer.ns[2];
+  } else if (!strcmp(key, "sst_get_probed")) {  // ... and its probe's pairs
+    *value = ctx->get_probed;
+  } else if (!strcmp(key, "sst_get_walked")) {
+    *value = ctx->get_walked;
   } else if (!strcmp(key, "mem_validate_ns")) {  // the last timed build's stages ("mem_build_time")
     *value = ctx->mem_timer.ns[0];
   } else if (!strcmp(key, "mem_chunk_ns")) {
@@ -2721,6 +2748,98 @@ int lsmck_sstable_merge_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_b
   }
   HIPCHK(hipStreamSynchronize(st));
   for (int k = 0; k < 4; ++k) HIPCHK(T.span(k, k + 1, k));
+  T.finish();
+  return 0;
+}
+
+int lsmck_sstable_get_batch(lsmck_ctx* ctx, const uint8_t* data, size_t data_bytes, const uint8_t* index,
+                            size_t index_bytes, const lsmck_sstable_span* spans, size_t ntab, const uint8_t* qkeys,
+                            size_t qkeys_bytes, const lsmck_get_query* q, size_t n, lsmck_get_result* res,
+                            uint64_t* bad_table, uint64_t* bad_query, unsigned flags) {
+  if (bad_table) *bad_table = ~0ull;
+  if (bad_query) *bad_query = ~0ull;
+  if (flags & ~(LSMCK_DEVICE | LSMCK_HOST_PINNED)) return lsmck_host::set_error(LSMCK_EINVAL, "sstable get: unknown flag");
+  if (n >= (1ull << 32) || ntab >= (1ull << 32))
+    return lsmck_host::set_error(LSMCK_EINVAL, "sstable get: more than 2^32-1 queries or tables in one batch");
+  if (ntab && !index) return lsmck_host::set_error(LSMCK_EINVAL, "sstable get: null index");
+  if ((ntab && !spans) || (n && (!q || !res)) || (data_bytes && !data) || (qkeys_bytes && !qkeys))
+    return lsmck_host::set_error(LSMCK_EINVAL, "sstable get: null spans, data, keys, queries or results");
+  if (!ctx) return mem_no_ctx("sstable get");
+  if (n == 0 && ntab == 0) return 0;
+  int rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DevGuard g(ctx->dev);
+  const hipStream_t st = ctx->stream0;
+  ScratchOrder so(ctx, st);
+  if (so.e != hipSuccess) return hip_error(so.e, "hipStreamWaitEvent(scratch)");
+  auto& G = ctx->get;
+  const bool dev = (flags & LSMCK_DEVICE) != 0;
+  if (!ntab) index_bytes = 0;
+  lsmck::GetArgs A{};
+  A.data = data, A.index = index, A.spans = spans, A.qkeys = qkeys, A.q = q;
+  if (!dev) {  // the host form is staged whole
+    if ((rc = G.data.ensure(data_bytes)) || (rc = G.index.ensure(index_bytes)) || (rc = G.spans.ensure(ntab)) ||
+        (rc = G.qkeys.ensure(qkeys_bytes)) || (rc = G.q.ensure(n)) || (rc = G.res.ensure(n)))
+      return rc;
+    if (data_bytes) HIPCHK(hipMemcpyAsync(G.data, data, data_bytes, hipMemcpyHostToDevice, st));
+    if (index_bytes) HIPCHK(hipMemcpyAsync(G.index, index, index_bytes, hipMemcpyHostToDevice, st));
+    if (ntab) HIPCHK(hipMemcpyAsync(G.spans, spans, ntab * sizeof(lsmck_sstable_span), hipMemcpyHostToDevice, st));
+    if (qkeys_bytes) HIPCHK(hipMemcpyAsync(G.qkeys, qkeys, qkeys_bytes, hipMemcpyHostToDevice, st));
+    if (n) HIPCHK(hipMemcpyAsync(G.q, q, n * sizeof(lsmck_get_query), hipMemcpyHostToDevice, st));
+    A.data = G.data, A.index = G.index, A.spans = G.spans, A.qkeys = G.qkeys, A.q = G.q;
+  }
+  A.data_bytes = data_bytes, A.index_bytes = index_bytes, A.qkeys_bytes = qkeys_bytes, A.ntab = ntab, A.n = n;
+  if ((rc = G.itemfirst.ensure(ntab + 1)) || (rc = G.bsum.ensure((size_t)lsmk_sst_scan_blocks(ntab) + 1)) ||
+      (rc = G.state.ensure(ntab)) || (rc = G.fail.ensure(ntab)) || (rc = G.qok.ensure(n)) || (rc = G.win.ensure(n)) ||
+      (rc = G.info.ensure(5)) || (rc = G.h_info.ensure(5, -1)))
+    return rc;
+  A.itemfirst = G.itemfirst, A.bsum = G.bsum, A.state = G.state, A.fail = G.fail, A.qok = G.qok, A.win = G.win;
+  A.info = G.info;
+  StageTimer& T = ctx->get_timer;
+  T.begin(ctx->opt.sst_encode_time);
+  A.count = T.on ? 1u : 0u;
+  // an index item is 16 bytes or more: the items' scratch is sized without a
+  // read-back, unless index spans overlap; then the first pass only counts
+  // and the passes run again
+  A.nslots = ntab ? index_bytes / 16 + ntab : 0;
+  for (int pass = 0;; ++pass) {
+    if ((rc = G.ioff.ensure((size_t)A.nslots)) || (rc = G.ipos.ensure((size_t)A.nslots)) ||
+        (rc = G.iok.ensure((size_t)A.nslots)))
+      return rc;
+    A.ioff = G.ioff, A.ipos = G.ipos, A.iok = G.iok;
+    HIPCHK(hipMemsetAsync(A.info, 0xFF, 16, st));
+    HIPCHK(hipMemsetAsync(A.info + 2, 0, 24, st));
+    // 1.-4. the index pass, the queries, the probe; the error words come back once
+    HIPCHK(T.mark(0, st));
+    if (ntab && (rc = lsmk_get_index(&A, st))) return launch_rc(rc, "sstable get index kernels");
+    HIPCHK(T.mark(1, st));
+    if (n && (rc = lsmk_get_probe(&A, st))) return launch_rc(rc, "sstable get probe kernels");
+    HIPCHK(T.mark(2, st));
+    HIPCHK(hipMemcpyAsync(G.h_info, A.info, 40, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (G.h_info[2] <= A.nslots) break;
+    if (pass) return lsmck_host::set_error(LSMCK_EINVAL, "sstable get: the index arena changed during the call");
+    A.nslots = G.h_info[2];
+  }
+  if (G.h_info[0] != ~0ull) {
+    if (bad_table) *bad_table = G.h_info[0];
+    return lsmck_host::set_error(LSMCK_EINVAL,
+                                 "sstable get: a table's span lies outside its arena, its data file is above 2^32-1 "
+                                 "bytes, or its index is not a map image with strictly increasing keys");
+  }
+  if (G.h_info[1] != ~0ull) {
+    if (bad_query) *bad_query = G.h_info[1];
+    return lsmck_host::set_error(LSMCK_EINVAL, "sstable get: a query's key lies outside qkeys, or its reserved is not 0");
+  }
+  if (T.on) ctx->get_probed = (long)G.h_info[3], ctx->get_walked = (long)G.h_info[4];
+  if (n == 0) return 0;
+  // 5. resolve
+  lsmck_get_result* dres = dev ? res : G.res.get();
+  if ((rc = lsmk_get_resolve(&A, dres, st))) return launch_rc(rc, "sstable get resolve kernel");
+  HIPCHK(T.mark(3, st));
+  if (!dev) HIPCHK(hipMemcpyAsync(res, dres, n * sizeof(lsmck_get_result), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int k = 0; k < 3; ++k) HIPCHK(T.span(k, k + 1, k));
   T.finish();
   return 0;
 }

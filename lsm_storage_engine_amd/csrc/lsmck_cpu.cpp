@@ -18,9 +18,11 @@
 #include <unistd.h>
 
 #include <string>
+#include <vector>
 
 #include "lsmck.h"
 #include "lsmck_internal.h"
+#include "lsmck_sstget.h"
 #include "lsmck_sstmerge.h"
 
 #if defined(__x86_64__)
@@ -490,6 +492,36 @@ uint64_t lsmck_sstable_count_records(const uint8_t* img, size_t n, uint64_t* con
   const uint64_t c = n ? lsmck::mrg::walk(img, n, 0, 0, ~0ull, nullptr, &end) : 0;
   if (consumed) *consumed = end;
   return c;
+}
+
+// SsTable::get on the calling thread: lsmck_sstget.h's steps in the kernels' order
+int lsmck_sstable_get(const uint8_t* data, size_t data_len, const uint8_t* index, size_t index_len,
+                      const uint8_t* key, uint32_t klen, uint64_t* val_off, uint32_t* vlen) {
+  namespace G = lsmck::get;
+  if (val_off) *val_off = 0;
+  if (vlen) *vlen = 0;
+  if (!val_off || !vlen) return lsmck_host::set_error(LSMCK_EINVAL, "sstable get: null val_off or vlen");
+  if (data_len > lsmck::mrg::kMaxTable)
+    return lsmck_host::set_error(LSMCK_EINVAL, "sstable get: the data file is above 2^32-1 bytes");
+  const uint64_t c = G::index_parse(index, index_len, nullptr, 0);
+  if (c == G::kNo) return lsmck_host::set_error(LSMCK_EINVAL, "sstable get: the index does not parse to its length");
+  std::vector<uint64_t> ioff((size_t)c), ipos((size_t)c);
+  std::vector<lsmck::mrg::OKey> ok((size_t)c);
+  (void)G::index_parse(index, index_len, ioff.data(), c);
+  for (uint64_t j = 0; j < c; ++j) {
+    ok[j] = G::item_okey(index, ioff[j]);
+    ipos[j] = G::item_pos(index, ioff[j]);
+    if (j && !G::item_less(index, ioff[j - 1], ioff[j]))
+      return lsmck_host::set_error(LSMCK_EINVAL, "sstable get: the index's keys do not strictly increase");
+  }
+  G::Table T;
+  T.img = data, T.dlen = data_len, T.idx = index, T.ok = ok.data(), T.ioff = ioff.data(), T.ipos = ipos.data();
+  T.nitems = c;
+  uint64_t vp;
+  uint32_t vl;
+  if (!G::table_get(T, G::key_of(key, 0, klen), &vp, &vl, nullptr)) return 0;
+  *val_off = vp, *vlen = vl;
+  return 1;
 }
 
 void lsmck_gen_zipf_lengths(uint64_t seed, double s, int kmax, uint32_t lmin, size_t n, uint32_t* out) {

@@ -123,10 +123,36 @@ struct MrgArgs {
   uint32_t mode;
   unsigned long long* info;
 };
+// The batch point read's arguments and scratch (lsmck_sstget.hip get_*).  Per
+// table: itemfirst (its index's items, then their exclusive scan: its place in
+// the item arrays; ntab + 1), state (kGet*), fail (bit 0: an item of a
+// one-length index was not where it was expected).  Per item slot (nslots):
+// ioff (its offset in its index image), ipos (its position), iok (its order
+// key).  Per query: qok (its order key), win (the lowest table that answered;
+// LSMCK_GET_NONE: none yet).  count: the probe counts its pairs.  info: 5
+// words -- [0] the first table refused and [1] the first query refused (atomic
+// min, set to ~0 by the caller), [2] the items of all tables, [3] the (query,
+// table) pairs probed and [4] those whose interval was walked (set to 0).
+struct GetArgs {
+  const uint8_t *data, *index, *qkeys;
+  uint64_t data_bytes, index_bytes, qkeys_bytes;
+  const lsmck_sstable_span* spans;
+  const lsmck_get_query* q;
+  uint64_t ntab, n, nslots;
+  uint64_t *itemfirst, *bsum, *ioff, *ipos;
+  mrg::OKey *iok, *qok;
+  uint32_t *state, *fail, *win;
+  uint32_t count;
+  unsigned long long* info;
+};
 
 }  // namespace lsmck
 
 extern "C" {
+// batch point read (lsmck_sstget.hip)
+int lsmk_get_index(const lsmck::GetArgs* a, hipStream_t st);  // spans, the map's parse, order, order keys (ntab > 0)
+int lsmk_get_probe(const lsmck::GetArgs* a, hipStream_t st);  // the queries' check, then every (query, table) pair
+int lsmk_get_resolve(const lsmck::GetArgs* a, lsmck_get_result* res, hipStream_t st);
 // batch SSTable decode and merge (lsmck_sstmerge.hip); ntab > 0 and n > 0
 int lsmk_dec_index(const lsmck::DecArgs* a, hipStream_t st);     // spans, index parse, segment starts
 int lsmk_dec_segments(const lsmck::DecArgs* a, hipStream_t st);  // the segments' check

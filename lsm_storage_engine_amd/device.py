@@ -153,6 +153,18 @@ class SstMergeError(_lib.LsmckError):
         super().__init__(rc, f"{what} (bad_index={bad_index}, needed={needed}, stuck={stuck})")
 
 
+class SstGetError(_lib.LsmckError):
+    """lsmck_sstable_get_batch refused the batch: ``bad_table`` is the first
+    table whose span or index is refused, else ``bad_query`` the first query
+    whose key range or reserved word is (LSMCK_EINVAL; both None for an
+    argument error)."""
+
+    def __init__(self, rc, what, bad_table=None, bad_query=None):
+        self.bad_table = bad_table
+        self.bad_query = bad_query
+        super().__init__(rc, f"{what} (bad_table={bad_table}, bad_query={bad_query})")
+
+
 class Context:
     def __init__(self, device=0):
         lib = _lib.load()
@@ -564,6 +576,44 @@ class Context:
         ngrp + 1); raises SstMergeError; nothing was written then."""
         return self._sst_merge(keys_ptr, keys_bytes, vals_ptr, vals_bytes, ents_ptr, n, tab_first, group_first, out_ptr,
                                cap, src_ptr, _lib.DEVICE, tombstones)
+
+    def _sst_get(self, data, db, index, ib, spans, ntab, qkeys, qb, q, n, res, flags):
+        none = 2 ** 64 - 1
+        bt, bq = C.c_uint64(none), C.c_uint64(none)
+        rc = self.lib.lsmck_sstable_get_batch(self.handle, data, db, index, ib, spans, ntab, qkeys, qb, q, n, res,
+                                              C.byref(bt), C.byref(bq), flags)
+        if rc == _lib.EINVAL:
+            raise SstGetError(rc, "sstable_get_batch", bad_table=None if bt.value == none else bt.value,
+                              bad_query=None if bq.value == none else bq.value)
+        _lib.check(rc, "sstable_get_batch")
+
+    def sstable_get_batch(self, data, index, spans, qkeys, queries, pinned=False):
+        """lsmck_sstable_get_batch, host form: SsTable::get of every query
+        (GET_QUERY_DTYPE: key ranges in the uint8 arena ``qkeys``) over the
+        tables whose data and index files lie in the uint8 arenas ``data`` and
+        ``index`` at ``spans`` (SSTABLE_SPAN_DTYPE, in search order), the first
+        table that answers winning.  Returns GET_RESULT_DTYPE per query:
+        ``table`` (GET_NONE: no table answered), ``val_off`` into ``data``
+        (bit 63, GET_TOMBSTONE: the value is the byte 0) and ``vlen``.  Raises
+        SstGetError (``bad_table`` or ``bad_query``)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        index = np.ascontiguousarray(index, dtype=np.uint8)
+        spans = np.ascontiguousarray(spans, dtype=_lib.SSTABLE_SPAN_DTYPE)
+        qkeys = np.ascontiguousarray(qkeys, dtype=np.uint8)
+        queries = np.ascontiguousarray(queries, dtype=_lib.GET_QUERY_DTYPE)
+        res = np.empty(len(queries), dtype=_lib.GET_RESULT_DTYPE)
+        self._sst_get(data.ctypes.data, data.nbytes, index.ctypes.data, index.nbytes, spans.ctypes.data, len(spans),
+                      qkeys.ctypes.data, qkeys.nbytes, queries.ctypes.data, len(queries), res.ctypes.data,
+                      _lib.HOST_PINNED if pinned else _lib.HOST)
+        return res
+
+    def sstable_get_batch_device(self, data_ptr, data_bytes, index_ptr, index_bytes, spans_ptr, ntab, qkeys_ptr,
+                                 qkeys_bytes, queries_ptr, n, res_ptr):
+        """lsmck_sstable_get_batch on device pointers (spans: ntab
+        lsmck_sstable_span; queries: n lsmck_get_query, 8-byte aligned; res: n
+        lsmck_get_result).  Raises SstGetError; nothing was written then."""
+        self._sst_get(data_ptr, data_bytes, index_ptr, index_bytes, spans_ptr, ntab, qkeys_ptr, qkeys_bytes, queries_ptr,
+                      n, res_ptr, _lib.DEVICE)
 
     def wal_recs_to_cmds_device(self, recs_ptr, n, img_bytes, cmds_ptr, stream=None):
         """lsmck_wal_recs_to_cmds: n compact replay records (lsmck_wal_rec16,

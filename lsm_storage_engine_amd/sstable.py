@@ -14,6 +14,11 @@ call (``lsmck_sstable_encode_batch``: the data and index images of every table
 and their SHA-256 digests).  Without a context the bytes are built here and
 hashed by the scalar path (``Checksums.write_checksums``); the files are the
 same either way.
+
+Reading them back: ``read_table`` (the iterator), ``merge_compact`` (the
+compaction) and the point read -- ``table_get``, SsTable::get literally, and
+``get_many``, Db::get's table loop for many keys, one
+``lsmck_sstable_get_batch`` with a context or the literal loop without one.
 """
 import ctypes as C
 import os
@@ -344,5 +349,125 @@ def merge_compact(base_path, level, tables, ctx=None, tombstones="stuck", timest
     return _write_table(m, *table_bytes(entries))
 
 
+class _TombstoneHit:
+    """get_many's result for a key whose first answer is a tombstone."""
+
+    def __repr__(self):
+        return "TOMBSTONE_HIT"
+
+
+TOMBSTONE_HIT = _TombstoneHit()
+
+
+def _read_record(image, pos):
+    """datafile.rs:60-83: ((key, value), record length) or None on UnexpectedEof."""
+    if pos > len(image) or len(image) - pos < 8:
+        return None
+    klen, vlen = struct.unpack_from("<II", image, pos)
+    if len(image) - pos - 8 < klen + vlen:
+        return None
+    return (image[pos + 8:pos + 8 + klen], image[pos + 8 + klen:pos + 8 + klen + vlen]), 8 + klen + vlen
+
+
+def index_map(index):
+    """The index file's BTreeMap<Vec<u8>, u64> (sstable_index.rs:20-25) as
+    (keys, positions) in key order.  Raises ValueError for an image that does
+    not parse to exactly its length or whose keys do not strictly increase:
+    the reference panics at load or never writes such a file, and
+    lsmck_sstable_get_batch refuses it."""
+    index = bytes(index)
+    if len(index) < 8:
+        raise ValueError("index: no count")
+    (count,), at, keys, pos = struct.unpack_from("<Q", index, 0), 8, [], []
+    for _ in range(count):
+        if len(index) - at < 16:
+            raise ValueError("index: an item is cut")
+        klen = struct.unpack_from("<Q", index, at)[0]
+        if klen > len(index) - at - 16:
+            raise ValueError("index: an item is cut")
+        key = index[at + 8:at + 8 + klen]
+        if keys and not keys[-1] < key:
+            raise ValueError("index: keys do not strictly increase")
+        keys.append(key)
+        pos.append(struct.unpack_from("<Q", index, at + 8 + klen)[0])
+        at += 16 + klen
+    if at != len(index):
+        raise ValueError("index: trailing bytes")
+    return keys, pos
+
+
+def table_get(data, index, key, _map=None):
+    """SsTable::get (src/sync/sstable.rs:97-113), literally, over a table's
+    data and index file images: the value, or None.  An exact index hit
+    returns the record at the item's position whatever its key is;
+    otherwise the records from the last item below the key are scanned, the
+    first one always read, until the position of the first item above it
+    (datafile.rs:85-103).  The bloom filter is not read (a filter built from
+    the table's own keys never changes a result)."""
+    import bisect
+    data, key = bytes(data), bytes(key)
+    keys, pos = index_map(index) if _map is None else _map
+    i = bisect.bisect_left(keys, key)
+    if i < len(keys) and keys[i] == key:
+        r = _read_record(data, pos[i])
+        return None if r is None else r[0][1]
+    p = pos[i - 1] if i > 0 else 0
+    end = pos[i] if i < len(keys) else len(data)
+    while True:
+        r = _read_record(data, p)
+        if r is None:
+            return None
+        if r[0][0] == key:
+            return r[0][1]
+        p += r[1]
+        if p >= end:
+            return None
+
+
+def get_many(levels, keys, ctx=None):
+    """Db::get_internal's table loop (src/tokio/db.rs:178-185) for many keys:
+    ``levels`` is a list of lists of SsTableMetadata in the reference's vector
+    order; every level is asked newest first (reversed), level 0 before level
+    1 and so on, and the first table whose get is Some answers.  With a
+    context the files are uploaded once and one lsmck_sstable_get_batch
+    answers every key; without one table_get runs in a loop.  Returns per key
+    the value, None (no table holds it) or TOMBSTONE_HIT (the first answer is
+    the tombstone ``[0]``: Db::get's other kind of "not found", db.rs:146-151).
+    The results are equal either way.  The memtables' step of Db::get stays
+    with the caller."""
+    keys = [bytes(k) for k in keys]
+    order = [m for level in levels for m in reversed(level)]
+    datas = [open(m.data_path(), "rb").read() for m in order]
+    idxs = [open(m.index_path(), "rb").read() for m in order]
+    if ctx is None:
+        maps = [index_map(x) for x in idxs]
+        out = []
+        for k in keys:
+            v = next((v for v in (table_get(d, None, k, m) for d, m in zip(datas, maps)) if v is not None), None)
+            out.append(TOMBSTONE_HIT if v == b"\x00" else v)
+        return out
+    spans = np.zeros(len(order), dtype=_lib.SSTABLE_SPAN_DTYPE)
+    spans["data_len"], spans["index_len"] = [len(d) for d in datas], [len(x) for x in idxs]
+    spans["data_off"] = np.cumsum(spans["data_len"]) - spans["data_len"]
+    spans["index_off"] = np.cumsum(spans["index_len"]) - spans["index_len"]
+    arena = b"".join(datas)
+    q = np.zeros(len(keys), dtype=_lib.GET_QUERY_DTYPE)
+    klen = np.fromiter((len(k) for k in keys), dtype=np.uint64, count=len(keys))
+    q["klen"], q["key_off"] = klen, np.cumsum(klen) - klen
+    res = ctx.sstable_get_batch(np.frombuffer(arena, np.uint8), np.frombuffer(b"".join(idxs), np.uint8), spans,
+                                np.frombuffer(b"".join(keys), np.uint8), q)
+    out = []
+    for r in res:
+        off = int(r["val_off"])
+        if int(r["table"]) == _lib.GET_NONE:
+            out.append(None)
+        elif off & _lib.GET_TOMBSTONE:
+            out.append(TOMBSTONE_HIT)
+        else:
+            out.append(arena[off:off + int(r["vlen"])])
+    return out
+
+
 __all__ = ["from_memtable", "flush_many", "flush_log_image", "table_bytes", "batch_arrays", "INDEX_STEP",
-           "iter_records", "read_table", "merge_loop", "merge_compact", "merge_compact_many", "MergeStuck"]
+           "iter_records", "read_table", "merge_loop", "merge_compact", "merge_compact_many", "MergeStuck", "index_map", "table_get",
+           "get_many", "TOMBSTONE_HIT"]
