@@ -285,8 +285,9 @@ int lsmck_device_count(void);
  *                 reads them back as stats); 0 = none (default).  It times
  *                 lsmck_sstable_decode_batch and lsmck_sstable_merge_batch
  *                 the same way (tools/merge_big.py), and
- *                 lsmck_sstable_get_batch (tools/get_big.py), whose probe
- *                 then also counts its pairs.
+ *                 lsmck_sstable_get_batch (tools/get_big.py) and
+ *                 lsmck_db_get_batch (tools/db_get_big.py), whose probes
+ *                 then also count their pairs.
  *   "mem_build_time"  DIAGNOSTIC, not part of the stable option list, as
  *                 "wal_encode_time": 1 = lsmck_memtable_build records device
  *                 events around its stages (tools/memtable_big.py reads them
@@ -349,6 +350,17 @@ int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value);
  *                    "sst_get_probed" / "sst_get_walked", the pairs that
  *                    probe looked up (the others were skipped behind a lower
  *                    table's answer) and those whose interval it walked.
+ *   "db_get_runs_ns", "db_get_index_ns", "db_get_run_probe_ns",
+ *   "db_get_probe_ns", "db_get_resolve_ns", "db_get_gather_ns"
+ *                    DIAGNOSTIC, subject to change: the last
+ *                    lsmck_db_get_batch's stages, with "sst_encode_time" 1:
+ *                    the run pass, the index pass, the queries' check and the
+ *                    probe of every (query, run) pair, the table probe,
+ *                    resolve and the lengths' scan, the gather; and
+ *                    "db_get_probed" / "db_get_walked", the (query, table)
+ *                    pairs its table probe looked up and those whose interval
+ *                    it walked, and "db_get_run_hits", the queries a run
+ *                    answered.
  *   "mem_rounds"     the chunk rounds the last lsmck_memtable_build ran (0 for
  *                    fewer than two commands; each round is a host round trip).
  *   "mem_validate_ns", "mem_chunk_ns", "mem_sort_ns", "mem_resolve_ns"
@@ -827,10 +839,10 @@ int lsmck_sstable_merge_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_b
  * over the order keys and the exact hit's read or the interval's walk of
  * headers, and lowers the query's winning table with an atomic minimum; a
  * thread per query repeats the lookup in the winning table and writes res.
- * Not covered: Db::get's memtable and old-memtable step (a host dict, or a
- * lower bound over lsmck_memtable_build's output), a resident "opened table"
- * form that keeps the index pass between calls, and sorting queries by
- * interval so that one walk serves many.
+ * Db::get's memtable and old-memtable step in front of these tables, and the
+ * values' bytes in one arena: lsmck_db_get_batch below.  Not covered: a
+ * resident "opened table" form that keeps the index pass between calls, and
+ * sorting queries by interval so that one walk serves many.
  * flags: LSMCK_DEVICE -- data, index, spans, qkeys, q (8-byte aligned) and res
  * are device pointers; LSMCK_HOST (optionally | LSMCK_HOST_PINNED, a hint
  * only) -- host pointers, staged whole.  Any other flag bit is LSMCK_EINVAL.
@@ -867,6 +879,79 @@ int lsmck_sstable_get_batch(lsmck_ctx* ctx, const uint8_t* data, size_t data_byt
  * vlen is NULL.  The index is parsed on every call (O(items)). */
 int lsmck_sstable_get(const uint8_t* data, size_t data_len, const uint8_t* index, size_t index_len,
                       const uint8_t* key, uint32_t klen, uint64_t* val_off, uint32_t* vlen);
+
+/* Batch Db::get: Db::get (src/tokio/db.rs:144-155) over Db::get_internal's
+ * whole search order (db.rs:156-189, src/sync/lsm_storage.rs:101) for many
+ * keys -- the memtable (db.rs:158-165), the old memtable (db.rs:166-173), then
+ * the table loop (db.rs:178-185) -- with the values optionally gathered into
+ * one packed arena.  A memtable is passed as a RUN: nent entries (the encode's
+ * entry type, type 1) strictly increasing in Vec<u8> order, their key and
+ * value ranges in the run's own two arenas (which may be one buffer) -- what
+ * lsmck_memtable_build leaves.  Every run has its own arenas because a
+ * memtable and an old memtable are separate buffers.
+ *   Sources.  Sources 0..nrun-1 are the runs in the order given (the caller
+ *     passes the memtable, then the old memtable); sources nrun..nrun+ntab-1
+ *     are the tables in lsmck_sstable_get_batch's search order.  The first
+ *     source whose get is Some answers.
+ *   Runs.  A run's get is BTreeMap::get (memtable.rs:68-70): an entry whose
+ *     key equals the query's key is Some(value).  An empty value counts, and
+ *     so does the one byte 0: it is what Db::delete puts there (db.rs:140).
+ *     A memtable rebuilt by from_log holds no tombstones -- its Removes erase
+ *     entries (memtable.rs:40-43) -- so lsmck_memtable_build's output has
+ *     none; a live memtable with deletes is built from Inserts of [0].
+ *   Tables.  A table's get is lsmck_sstable_get_batch's, word for word: the
+ *     same code, quirks included (see above).
+ *   Results.  res[i].table is the source number or LSMCK_GET_NONE; val_off is
+ *     relative to the winning run's `vals` (0 for an empty value: its offset
+ *     is not looked at) or to `data`; the tombstone bit is set as above.  With
+ *     nrun == 0 the results are byte-identical to lsmck_sstable_get_batch's.
+ *   Gather (out_off != NULL).  out_off[0..n] is the exclusive scan of the
+ *     answered lengths and out[out_off[i] .. out_off[i+1]) holds query i's
+ *     value under Db::get's rule (db.rs:146-151): a tombstone winner or no
+ *     winner contributes 0 bytes (res tells them apart from an empty value).
+ *     A key asked twice is gathered twice.  *out_bytes = out_off[n].
+ * On the device (lsmck_dbget.hip, lsmck_dbget.h): a thread per run entry
+ * checks it, forms its 16-byte order key and proves it above its predecessor;
+ * a work item per (query, run) pair does a lower bound over the order keys
+ * (the arenas are read only on a tie past 8 bytes) before the table probe
+ * starts, so a key a run answered walks no index interval; a thread per query
+ * resolves its winner into scratch and the lengths are scanned there; the
+ * error words and the total come back once; the gather is output-centric as
+ * the encodes' are -- out cut into 32 KiB tiles aligned on its address, a lane
+ * storing aligned 16-byte chunks once each, sources at any alignment.
+ * flags: LSMCK_DEVICE -- every pointer inside the run descriptors, data, index,
+ * spans, qkeys, q, res, out and out_off are device pointers (ents, q, res and
+ * out_off 8-byte aligned); LSMCK_HOST (optionally | LSMCK_HOST_PINNED, a hint
+ * only) -- host pointers, staged whole.  `runs` itself (nrun descriptors),
+ * out_bytes and the bad_* words are host pointers either way; the bad_* words
+ * may be NULL and are set to UINT64_MAX unless they name something.
+ * Synchronous; scratch comes from the context.
+ * Returns 0 (n == 0 with out_off: out_off[0] = 0), or, checked in this order,
+ *   LSMCK_EINVAL  with *bad_run_entry = the first offending run entry, counted
+ *                 across the runs: it fails the encode's entry rule (type 1,
+ *                 8 + klen + vlen <= 2^32-1, non-empty ranges inside its own
+ *                 run's arenas) or its key is not strictly above its
+ *                 predecessor's in its run; else
+ *                 with *bad_table, as lsmck_sstable_get_batch; else
+ *                 with *bad_query, as lsmck_sstable_get_batch; or
+ *                 with all three UINT64_MAX (checked before any GPU work): n,
+ *                 ntab, nrun or the runs' entries together are 2^32 or more, a
+ *                 null array that is needed, out_off without out_bytes, or a
+ *                 wrong flag.
+ *   LSMCK_ENOSPC  out_cap is smaller than the gathered bytes: *out_bytes is
+ *                 the size needed.
+ *   LSMCK_ENODEV  there is no GPU (and so no context).
+ * On any error no byte of res, out_off or out is written. */
+typedef struct {
+  const uint8_t* keys; uint64_t keys_bytes;   /* the run's arenas (may be one buffer) */
+  const uint8_t* vals; uint64_t vals_bytes;
+  const lsmck_wal_cmd* ents; uint64_t nent;   /* type 1, strictly increasing in Vec<u8> order */
+} lsmck_get_run;                              /* 48 bytes; the array itself is always a HOST array of nrun */
+int lsmck_db_get_batch(lsmck_ctx* ctx, const lsmck_get_run* runs, size_t nrun, const uint8_t* data, size_t data_bytes,
+                       const uint8_t* index, size_t index_bytes, const lsmck_sstable_span* spans, size_t ntab,
+                       const uint8_t* qkeys, size_t qkeys_bytes, const lsmck_get_query* q, size_t n,
+                       lsmck_get_result* res, uint8_t* out, size_t out_cap, uint64_t* out_off, uint64_t* out_bytes,
+                       uint64_t* bad_run_entry, uint64_t* bad_table, uint64_t* bad_query, unsigned flags);
 
 /* Whole-tree SSTable verify: the batch form of Checksums::verify over many
  * tables (Db::load, src/tokio/db.rs:37-59 -> src/tokio/sstable.rs:34).

@@ -99,6 +99,10 @@ GET_RESULT_DTYPE = np.dtype([("val_off", "<u8"), ("vlen", "<u4"), ("table", "<u4
 assert GET_QUERY_DTYPE.itemsize == GET_RESULT_DTYPE.itemsize == 16
 GET_NONE = 0xFFFFFFFF  # LSMCK_GET_NONE: lsmck_get_result.table when no table answered
 GET_TOMBSTONE = 1 << 63  # LSMCK_GET_TOMBSTONE: bit 63 of lsmck_get_result.val_off
+# include/lsmck.h lsmck_get_run (48 bytes, no padding): one run of lsmck_db_get_batch, its pointers as integers
+GET_RUN_DTYPE = np.dtype([("keys", "<u8"), ("keys_bytes", "<u8"), ("vals", "<u8"), ("vals_bytes", "<u8"),
+                          ("ents", "<u8"), ("nent", "<u8")])
+assert GET_RUN_DTYPE.itemsize == 48
 
 
 class TreeReport(C.Structure):
@@ -166,6 +170,8 @@ SIGNATURES = [
     ("lsmck_sstable_get_batch", C.c_int,  # q: lsmck_get_query[n]; res: lsmck_get_result[n]; bad_table, bad_query: host
      [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, u64p, u64p, C.c_uint]),
     ("lsmck_sstable_get", C.c_int, [vp, sz, vp, sz, vp, C.c_uint32, u64p, u32p]),
+    ("lsmck_db_get_batch", C.c_int,  # runs: host lsmck_get_run[nrun]; out_off: u64[n + 1] or NULL; the last four: host
+     [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, vp, sz, vp, u64p, u64p, u64p, u64p, C.c_uint]),
     ("lsmck_checksums_verify_many", C.c_int,
      [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), sz, C.POINTER(C.c_int)]),
     ("lsmck_tree_verify", C.c_int, [vp, C.c_char_p, C.POINTER(TreeReport)]),

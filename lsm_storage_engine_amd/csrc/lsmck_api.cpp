@@ -290,9 +290,9 @@ constexpr int kHostSlots = 2;  // slots the host batches and the WAL upload alte
 // events are created when first recorded; the spans add up over the call and
 // become the stats only when it finishes.
 struct StageTimer {
-  hipEvent_t ev[7] = {};
-  double acc[4] = {0, 0, 0, 0};
-  long ns[4] = {0, 0, 0, 0};  // the last timed call's stages
+  hipEvent_t ev[8] = {};
+  double acc[6] = {0, 0, 0, 0, 0, 0};
+  long ns[6] = {0, 0, 0, 0, 0, 0};  // the last timed call's stages (four, or lsmck_db_get_batch's six)
   bool on = false;            // this call is timed
   void begin(bool timed) {
     on = timed;
@@ -315,7 +315,7 @@ struct StageTimer {
   }
   void finish() {
     if (on)
-      for (int k = 0; k < 4; ++k) ns[k] = (long)acc[k];
+      for (int k = 0; k < 6; ++k) ns[k] = (long)acc[k];
   }
   hipError_t finish4() {  // the two encodes' stages: events 0-1, 2-3, 3-4, 4-5
     const int pair[4][2] = {{0, 1}, {2, 3}, {3, 4}, {4, 5}};
@@ -472,6 +472,23 @@ struct lsmck_ctx {
   StageTimer get_timer;  // "sst_encode_time" (this call too): index pass, queries / probe, resolve
   long get_probed = 0;   // the last timed read's (query, table) pairs looked up
   long get_walked = 0;   // ... whose interval was walked
+  // batch Db::get (lsmck_device.h DbArgs; the tables' part is `get` above):
+  // the run descriptors and their nent scan on the device and their pinned
+  // source, the run entries' order keys, per query the result, the answered
+  // length / its scan and the value's address; host form: the runs' arenas
+  // and entries in one block, and the gathered values
+  struct {
+    DevBuf<lsmck_get_run> runs;
+    DevBuf<uint64_t> rf, len, src;
+    DevBuf<lsmck::mrg::OKey> rok;
+    DevBuf<lsmck_get_result> res;
+    DevBuf<uint8_t> stage, out;
+    PinBuf<uint8_t> h_runs;
+  } dbg;
+  StageTimer dbg_timer;  // "sst_encode_time" (this call too): run pass, index pass, run probe, table probe, resolve / scan, gather
+  long dbg_probed = 0;   // the last timed call's (query, table) pairs looked up
+  long dbg_walked = 0;   // ... whose interval was walked
+  long dbg_run_hits = 0;  // ... and its queries a run answered
   bool wal_recs_direct = false;  // this replay's records go by DMA into the caller's pinned array (under wal_mu)
   bool wal_compact = false;      // this replay's records are lsmck_wal_rec16 (under wal_mu)
   // LSMCK_RECS_DEVICE (under wal_mu): the caller's device array and its capacity
@@ -1079,6 +1096,24 @@ int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value) {
     *value = ctx->get_timer.ns[1];
   } else if (!strcmp(key, "sst_get_resolve_ns")) {
     *value = ctx->get_timer.ns[2];
+  } else if (!strcmp(key, "db_get_runs_ns")) {  // the last timed batch Db::get's stages ("sst_encode_time")
+    *value = ctx->dbg_timer.ns[0];
+  } else if (!strcmp(key, "db_get_index_ns")) {
+    *value = ctx->dbg_timer.ns[1];
+  } else if (!strcmp(key, "db_get_run_probe_ns")) {
+    *value = ctx->dbg_timer.ns[2];
+  } else if (!strcmp(key, "db_get_probe_ns")) {
+    *value = ctx->dbg_timer.ns[3];
+  } else if (!strcmp(key, "db_get_resolve_ns")) {
+    *value = ctx->dbg_timer.ns[4];
+  } else if (!strcmp(key, "db_get_gather_ns")) {
+    *value = ctx->dbg_timer.ns[5];
+  } else if (!strcmp(key, "db_get_probed")) {  // ... and its probes' pairs
+    *value = ctx->dbg_probed;
+  } else if (!strcmp(key, "db_get_walked")) {
+    *value = ctx->dbg_walked;
+  } else if (!strcmp(key, "db_get_run_hits")) {
+    *value = ctx->dbg_run_hits;
   } else if (!strcmp(key, "sst_get_probed")) {  // ... and its probe's pairs
     *value = ctx->get_probed;
   } else if (!strcmp(key, "sst_get_walked")) {
@@ -2840,6 +2875,185 @@ int lsmck_sstable_get_batch(lsmck_ctx* ctx, const uint8_t* data, size_t data_byt
   if (!dev) HIPCHK(hipMemcpyAsync(res, dres, n * sizeof(lsmck_get_result), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   for (int k = 0; k < 3; ++k) HIPCHK(T.span(k, k + 1, k));
+  T.finish();
+  return 0;
+}
+
+int lsmck_db_get_batch(lsmck_ctx* ctx, const lsmck_get_run* runs, size_t nrun, const uint8_t* data, size_t data_bytes,
+                       const uint8_t* index, size_t index_bytes, const lsmck_sstable_span* spans, size_t ntab,
+                       const uint8_t* qkeys, size_t qkeys_bytes, const lsmck_get_query* q, size_t n,
+                       lsmck_get_result* res, uint8_t* out, size_t out_cap, uint64_t* out_off, uint64_t* out_bytes,
+                       uint64_t* bad_run_entry, uint64_t* bad_table, uint64_t* bad_query, unsigned flags) {
+  if (bad_run_entry) *bad_run_entry = ~0ull;
+  if (bad_table) *bad_table = ~0ull;
+  if (bad_query) *bad_query = ~0ull;
+  if (out_bytes) *out_bytes = 0;
+  if (flags & ~(LSMCK_DEVICE | LSMCK_HOST_PINNED)) return lsmck_host::set_error(LSMCK_EINVAL, "db get: unknown flag");
+  if (n >= (1ull << 32) || ntab >= (1ull << 32) || nrun >= (1ull << 32))
+    return lsmck_host::set_error(LSMCK_EINVAL, "db get: more than 2^32-1 queries, tables or runs in one batch");
+  if (nrun && !runs) return lsmck_host::set_error(LSMCK_EINVAL, "db get: null runs");
+  uint64_t nent = 0;
+  for (size_t r = 0; r < nrun; ++r) {
+    if (runs[r].nent >= (1ull << 32) || (nent += runs[r].nent) >= (1ull << 32))
+      return lsmck_host::set_error(LSMCK_EINVAL, "db get: more than 2^32-1 run entries in one batch");
+    if ((runs[r].nent && !runs[r].ents) || (runs[r].keys_bytes && !runs[r].keys) || (runs[r].vals_bytes && !runs[r].vals))
+      return lsmck_host::set_error(LSMCK_EINVAL, "db get: null entries, keys or values in a run");
+  }
+  if (ntab && !index) return lsmck_host::set_error(LSMCK_EINVAL, "db get: null index");
+  if ((ntab && !spans) || (n && (!q || !res)) || (data_bytes && !data) || (qkeys_bytes && !qkeys))
+    return lsmck_host::set_error(LSMCK_EINVAL, "db get: null spans, data, keys, queries or results");
+  if (out_off && !out_bytes) return lsmck_host::set_error(LSMCK_EINVAL, "db get: null out_bytes with out_off");
+  if (out_off && out_cap && !out) return lsmck_host::set_error(LSMCK_EINVAL, "db get: null out");
+  if (!ctx) return mem_no_ctx("db get");
+  int rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DevGuard g(ctx->dev);
+  const hipStream_t st = ctx->stream0;
+  ScratchOrder so(ctx, st);
+  if (so.e != hipSuccess) return hip_error(so.e, "hipStreamWaitEvent(scratch)");
+  auto& G = ctx->get;
+  auto& D = ctx->dbg;
+  const bool dev = (flags & LSMCK_DEVICE) != 0;
+  const bool gather = out_off != nullptr;
+  if (!ntab) index_bytes = 0;
+  lsmck::DbArgs B{};
+  lsmck::GetArgs& A = B.g;
+  A.data = data, A.index = index, A.spans = spans, A.qkeys = qkeys, A.q = q;
+  // the descriptors and the scan of their nent, from a pinned block (the copy is asynchronous)
+  const size_t desc_bytes = nrun * sizeof(lsmck_get_run), rf_bytes = (nrun + 1) * 8;
+  if ((rc = D.h_runs.ensure(desc_bytes + rf_bytes, -1)) || (rc = D.runs.ensure(nrun)) || (rc = D.rf.ensure(nrun + 1)))
+    return rc;
+  lsmck_get_run* hr = (lsmck_get_run*)D.h_runs.get();
+  uint64_t* hrf = (uint64_t*)(D.h_runs.get() + desc_bytes);
+  hrf[0] = 0;
+  for (size_t r = 0; r < nrun; ++r) hr[r] = runs[r], hrf[r + 1] = hrf[r] + runs[r].nent;
+  if (!dev) {  // the host form is staged whole
+    if ((rc = G.data.ensure(data_bytes)) || (rc = G.index.ensure(index_bytes)) || (rc = G.spans.ensure(ntab)) ||
+        (rc = G.qkeys.ensure(qkeys_bytes)) || (rc = G.q.ensure(n)))
+      return rc;
+    if (data_bytes) HIPCHK(hipMemcpyAsync(G.data, data, data_bytes, hipMemcpyHostToDevice, st));
+    if (index_bytes) HIPCHK(hipMemcpyAsync(G.index, index, index_bytes, hipMemcpyHostToDevice, st));
+    if (ntab) HIPCHK(hipMemcpyAsync(G.spans, spans, ntab * sizeof(lsmck_sstable_span), hipMemcpyHostToDevice, st));
+    if (qkeys_bytes) HIPCHK(hipMemcpyAsync(G.qkeys, qkeys, qkeys_bytes, hipMemcpyHostToDevice, st));
+    if (n) HIPCHK(hipMemcpyAsync(G.q, q, n * sizeof(lsmck_get_query), hipMemcpyHostToDevice, st));
+    A.data = G.data, A.index = G.index, A.spans = G.spans, A.qkeys = G.qkeys, A.q = G.q;
+    // every run's arenas and entries in one block, each piece at a multiple of 256
+    auto up = [](size_t x) { return (x + 255u) & ~(size_t)255u; };
+    size_t need = 0;
+    for (size_t r = 0; r < nrun; ++r) {
+      const bool one = runs[r].keys == runs[r].vals && runs[r].keys_bytes == runs[r].vals_bytes;
+      need += up(runs[r].keys_bytes) + (one ? 0 : up(runs[r].vals_bytes)) + up(runs[r].nent * sizeof(lsmck_wal_cmd));
+    }
+    if ((rc = D.stage.ensure(need))) return rc;
+    size_t at = 0;
+    for (size_t r = 0; r < nrun; ++r) {
+      const lsmck_get_run& R = runs[r];
+      const bool one = R.keys == R.vals && R.keys_bytes == R.vals_bytes;
+      hr[r].keys = D.stage.get() + at;
+      if (R.keys_bytes) HIPCHK(hipMemcpyAsync(D.stage.get() + at, R.keys, R.keys_bytes, hipMemcpyHostToDevice, st));
+      at += up(R.keys_bytes);
+      hr[r].vals = one ? hr[r].keys : D.stage.get() + at;
+      if (!one) {
+        if (R.vals_bytes) HIPCHK(hipMemcpyAsync(D.stage.get() + at, R.vals, R.vals_bytes, hipMemcpyHostToDevice, st));
+        at += up(R.vals_bytes);
+      }
+      hr[r].ents = (const lsmck_wal_cmd*)(D.stage.get() + at);
+      if (R.nent)
+        HIPCHK(hipMemcpyAsync(D.stage.get() + at, R.ents, R.nent * sizeof(lsmck_wal_cmd), hipMemcpyHostToDevice, st));
+      at += up(R.nent * sizeof(lsmck_wal_cmd));
+    }
+  }
+  if (nrun) HIPCHK(hipMemcpyAsync(D.runs, hr, desc_bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(D.rf, hrf, rf_bytes, hipMemcpyHostToDevice, st));
+  A.data_bytes = data_bytes, A.index_bytes = index_bytes, A.qkeys_bytes = qkeys_bytes, A.ntab = ntab, A.n = n;
+  A.base = (uint32_t)nrun;
+  const size_t nb = (size_t)std::max(lsmk_sst_scan_blocks(ntab), lsmk_sst_scan_blocks(n)) + 1;
+  if ((rc = G.itemfirst.ensure(ntab + 1)) || (rc = G.bsum.ensure(nb)) || (rc = G.state.ensure(ntab)) ||
+      (rc = G.fail.ensure(ntab)) || (rc = G.qok.ensure(n)) || (rc = G.win.ensure(n)) || (rc = G.info.ensure(8)) ||
+      (rc = G.h_info.ensure(8, -1)) || (rc = D.rok.ensure((size_t)nent)) || (rc = D.res.ensure(n)) ||
+      (gather && ((rc = D.len.ensure(n + 1)) || (rc = D.src.ensure(n)))))
+    return rc;
+  A.itemfirst = G.itemfirst, A.bsum = G.bsum, A.state = G.state, A.fail = G.fail, A.qok = G.qok, A.win = G.win;
+  A.info = G.info;
+  B.runs = D.runs, B.rf = D.rf, B.nrun = nrun, B.nent = nent, B.rok = D.rok, B.res = D.res;
+  B.len = gather ? D.len.get() : nullptr, B.src = gather ? D.src.get() : nullptr;
+  StageTimer& T = ctx->dbg_timer;
+  T.begin(ctx->opt.sst_encode_time);
+  A.count = T.on ? 1u : 0u;
+  // the items' scratch: as lsmck_sstable_get_batch sizes it
+  A.nslots = ntab ? index_bytes / 16 + ntab : 0;
+  for (int pass = 0;; ++pass) {
+    if ((rc = G.ioff.ensure((size_t)A.nslots)) || (rc = G.ipos.ensure((size_t)A.nslots)) ||
+        (rc = G.iok.ensure((size_t)A.nslots)))
+      return rc;
+    A.ioff = G.ioff, A.ipos = G.ipos, A.iok = G.iok;
+    HIPCHK(hipMemsetAsync(A.info, 0xFF, 16, st));
+    HIPCHK(hipMemsetAsync(A.info + 2, 0, 24, st));
+    HIPCHK(hipMemsetAsync(A.info + 5, 0xFF, 8, st));
+    HIPCHK(hipMemsetAsync(A.info + 6, 0, 16, st));
+    // 1.-5. everything up to the lengths' scan; the error words and the total come back once
+    HIPCHK(T.mark(0, st));
+    if (nent && (rc = lsmk_dbg_runs(&B, st))) return launch_rc(rc, "db get run pass kernel");
+    HIPCHK(T.mark(1, st));
+    if (ntab && (rc = lsmk_get_index(&A, st))) return launch_rc(rc, "db get index kernels");
+    HIPCHK(T.mark(2, st));
+    if (n && (rc = lsmk_get_queries(&A, st))) return launch_rc(rc, "db get query kernel");
+    if (n && nent && (rc = lsmk_dbg_probe(&B, st))) return launch_rc(rc, "db get run probe kernel");
+    HIPCHK(T.mark(3, st));
+    if (n && (rc = lsmk_get_pairs(&A, st))) return launch_rc(rc, "db get table probe kernel");
+    HIPCHK(T.mark(4, st));
+    if (n && (rc = lsmk_dbg_resolve(&B, st))) return launch_rc(rc, "db get resolve / scan kernels");
+    HIPCHK(T.mark(5, st));
+    HIPCHK(hipMemcpyAsync(G.h_info, A.info, 64, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (G.h_info[2] <= A.nslots) break;
+    if (pass) return lsmck_host::set_error(LSMCK_EINVAL, "db get: the index arena changed during the call");
+    A.nslots = G.h_info[2];
+  }
+  if (G.h_info[5] != ~0ull) {
+    if (bad_run_entry) *bad_run_entry = G.h_info[5];
+    return lsmck_host::set_error(LSMCK_EINVAL,
+                                 "db get: invalid run entry (type, lengths, a range outside its run's arenas, or a key "
+                                 "not above its predecessor's)");
+  }
+  if (G.h_info[0] != ~0ull) {
+    if (bad_table) *bad_table = G.h_info[0];
+    return lsmck_host::set_error(LSMCK_EINVAL,
+                                 "db get: a table's span lies outside its arena, its data file is above 2^32-1 bytes, "
+                                 "or its index is not a map image with strictly increasing keys");
+  }
+  if (G.h_info[1] != ~0ull) {
+    if (bad_query) *bad_query = G.h_info[1];
+    return lsmck_host::set_error(LSMCK_EINVAL, "db get: a query's key lies outside qkeys, or its reserved is not 0");
+  }
+  const uint64_t total = gather && n ? G.h_info[7] : 0;
+  if (gather) {
+    *out_bytes = total;
+    if (out_cap < total) return lsmck_host::set_error(LSMCK_ENOSPC, "db get: out_cap is smaller than the values");
+  }
+  if (T.on) ctx->dbg_probed = (long)G.h_info[3], ctx->dbg_walked = (long)G.h_info[4], ctx->dbg_run_hits = (long)G.h_info[6];
+  if (n == 0) {  // (no result; the scan of no lengths)
+    if (gather && dev) HIPCHK(hipMemsetAsync(out_off, 0, 8, st));
+    if (gather && dev) HIPCHK(hipStreamSynchronize(st));
+    if (gather && !dev) out_off[0] = 0;
+    return 0;
+  }
+  // 6. the gather; res and out_off from scratch
+  uint8_t* dout = out;
+  if (gather && !dev && total) {
+    if ((rc = D.out.ensure((size_t)total))) return rc;
+    dout = D.out;
+  }
+  HIPCHK(T.mark(6, st));  // (behind the read-back: the gather's stage holds no host round trip)
+  if (gather && (rc = lsmk_dbg_gather(&B, dout, total, st))) return launch_rc(rc, "db get gather kernel");
+  HIPCHK(T.mark(7, st));
+  const hipMemcpyKind back = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  HIPCHK(hipMemcpyAsync(res, B.res, n * sizeof(lsmck_get_result), back, st));
+  if (gather) HIPCHK(hipMemcpyAsync(out_off, B.len, (n + 1) * 8, back, st));
+  if (gather && !dev && total) HIPCHK(hipMemcpyAsync(out, dout, (size_t)total, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int k = 0; k < 5; ++k) HIPCHK(T.span(k, k + 1, k));
+  HIPCHK(T.span(6, 7, 5));
   T.finish();
   return 0;
 }

@@ -129,10 +129,12 @@ struct MrgArgs {
 // one-length index was not where it was expected).  Per item slot (nslots):
 // ioff (its offset in its index image), ipos (its position), iok (its order
 // key).  Per query: qok (its order key), win (the lowest table that answered;
-// LSMCK_GET_NONE: none yet).  count: the probe counts its pairs.  info: 5
-// words -- [0] the first table refused and [1] the first query refused (atomic
-// min, set to ~0 by the caller), [2] the items of all tables, [3] the (query,
-// table) pairs probed and [4] those whose interval was walked (set to 0).
+// LSMCK_GET_NONE: none yet).  count: the probe counts its pairs.  base: the
+// number of table 0 as a source in win (0; lsmck_db_get_batch's runs come in
+// front of the tables).  info: 5 words -- [0] the first table refused and [1]
+// the first query refused (atomic min, set to ~0 by the caller), [2] the items
+// of all tables, [3] the (query, table) pairs probed and [4] those whose
+// interval was walked (set to 0).
 struct GetArgs {
   const uint8_t *data, *index, *qkeys;
   uint64_t data_bytes, index_bytes, qkeys_bytes;
@@ -144,14 +146,41 @@ struct GetArgs {
   uint32_t *state, *fail, *win;
   uint32_t count;
   unsigned long long* info;
+  uint32_t base;
+};
+// The batch Db::get's (lsmck_dbget.hip dbg_*): the point read's arguments --
+// g.base = nrun, g.info holding 8 words -- and the runs.  runs: the
+// descriptors on the device; rf: the exclusive scan of their nent (nrun + 1);
+// nent = rf[nrun]; rok: every run entry's order key.  Per query: res (the
+// results, scratch until the error words are back), len (its answered length,
+// then the lengths' exclusive scan; n + 1; null without a gather) and src (its
+// value's address).  g.info[5] = the first run entry refused (atomic min, set
+// to ~0 by the caller), [6] the queries a run answered (set to 0), [7] the
+// gathered bytes.
+struct DbArgs {
+  GetArgs g;
+  const lsmck_get_run* runs;
+  const uint64_t* rf;
+  uint64_t nrun, nent;
+  mrg::OKey* rok;
+  lsmck_get_result* res;
+  uint64_t *len, *src;
 };
 
 }  // namespace lsmck
 
 extern "C" {
+// batch Db::get (lsmck_dbget.hip); the index pass and the table probe are the point read's
+int lsmk_dbg_runs(const lsmck::DbArgs* a, hipStream_t st);     // the run entries' check, order keys, order (nent > 0)
+int lsmk_dbg_probe(const lsmck::DbArgs* a, hipStream_t st);    // every (query, run) pair (n > 0, nent > 0)
+int lsmk_dbg_resolve(const lsmck::DbArgs* a, hipStream_t st);  // res, len / src and the lengths' scan (n > 0)
+int lsmk_dbg_gather(const lsmck::DbArgs* a, uint8_t* out, uint64_t total, hipStream_t st);
 // batch point read (lsmck_sstget.hip)
 int lsmk_get_index(const lsmck::GetArgs* a, hipStream_t st);  // spans, the map's parse, order, order keys (ntab > 0)
 int lsmk_get_probe(const lsmck::GetArgs* a, hipStream_t st);  // the queries' check, then every (query, table) pair
+// lsmk_get_probe's two halves, for lsmck_db_get_batch, whose run probe goes between them
+int lsmk_get_queries(const lsmck::GetArgs* a, hipStream_t st);  // the queries' check, order keys, win = none (n > 0)
+int lsmk_get_pairs(const lsmck::GetArgs* a, hipStream_t st);    // every (query, table) pair: a winner is a->base + t
 int lsmk_get_resolve(const lsmck::GetArgs* a, lsmck_get_result* res, hipStream_t st);
 // batch SSTable decode and merge (lsmck_sstmerge.hip); ntab > 0 and n > 0
 int lsmk_dec_index(const lsmck::DecArgs* a, hipStream_t st);     // spans, index parse, segment starts

@@ -239,4 +239,34 @@ LSMCK_ENC_HD lsmck_get_result result_none() {
 
 }  // namespace get
 }  // namespace lsmck
+
+#if defined(__HIPCC__)
+#include "lsmck_device.h"
+namespace lsmck {
+namespace get {
+// table t and query i of a call's arguments, for the kernels of
+// lsmck_sstget.hip and lsmck_dbget.hip
+__device__ __forceinline__ Table table_at(const GetArgs& a, uint64_t t) {
+  const lsmck_sstable_span s = a.spans[t];
+  const uint64_t f = a.itemfirst[t];
+  Table T;
+  T.img = a.data + s.data_off;
+  T.dlen = s.data_len;
+  T.idx = a.index + s.index_off;
+  T.ok = a.iok + f;
+  T.ioff = a.ioff + f;
+  T.ipos = a.ipos + f;
+  T.nitems = a.itemfirst[t + 1] - f;
+  return T;
+}
+__device__ __forceinline__ Key key_at(const GetArgs& a, uint64_t i) {
+  const lsmck_get_query q = a.q[i];
+  Key k;
+  k.p = q.klen ? a.qkeys + q.key_off : a.qkeys;
+  k.ok = a.qok[i];
+  return k;
+}
+}  // namespace get
+}  // namespace lsmck
+#endif
 #endif

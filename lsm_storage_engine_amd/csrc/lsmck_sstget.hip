@@ -16,9 +16,10 @@
 //      get_probe, the hot path: a work item per (query, table) pair, table
 //      major -- a lower bound over the table's order keys, then the exact
 //      hit's record or the interval's walk of headers; a Some lowers the
-//      query's winning table with a vector atomicMin.  A pair whose table lies
-//      above the current winner is skipped: that only saves work, the minimum
-//      stands however the reads race;
+//      query's winning source (the table's number above a.base: 0 here, the
+//      runs in front of the tables for lsmck_db_get_batch) with a vector
+//      atomicMin.  A pair whose table lies above the current winner is
+//      skipped: that only saves work, the minimum stands however the reads race;
 //      -- the error words are read back here, once --
 //   5. get_resolve: a thread per query repeats the lookup in its winning table
 //      alone and writes the result.
@@ -120,40 +121,19 @@ __global__ __launch_bounds__(256) void get_queries(GetArgs a) {
   a.win[i] = get::kNoTable;
 }
 
-__device__ __forceinline__ get::Table get_table(const GetArgs& a, uint64_t t) {
-  const lsmck_sstable_span s = a.spans[t];
-  const uint64_t f = a.itemfirst[t];
-  get::Table T;
-  T.img = a.data + s.data_off;
-  T.dlen = s.data_len;
-  T.idx = a.index + s.index_off;
-  T.ok = a.iok + f;
-  T.ioff = a.ioff + f;
-  T.ipos = a.ipos + f;
-  T.nitems = a.itemfirst[t + 1] - f;
-  return T;
-}
-__device__ __forceinline__ get::Key get_key(const GetArgs& a, uint64_t i) {
-  const lsmck_get_query q = a.q[i];
-  get::Key k;
-  k.p = q.klen ? a.qkeys + q.key_off : a.qkeys;
-  k.ok = a.qok[i];
-  return k;
-}
-
 // 4b. the (query, table) pairs, table major: pair w = t * n + i
 __global__ __launch_bounds__(256) void get_probe(GetArgs a) {
   if (a.info[0] != kGetNo || a.info[1] != kGetNo || !get_fits(a)) return;  // (the call fails: nothing is looked up)
   const uint64_t total = a.n * a.ntab, stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < total; w += stride) {
     const uint64_t t = w / a.n, i = w - t * a.n;
-    if (t > __atomic_load_n(a.win + i, __ATOMIC_RELAXED)) continue;  // (a lower table answered already)
-    const get::Table T = get_table(a, t);
-    const get::Key k = get_key(a, i);
+    if (a.base + t > __atomic_load_n(a.win + i, __ATOMIC_RELAXED)) continue;  // (a lower source answered already)
+    const get::Table T = get::table_at(a, t);
+    const get::Key k = get::key_at(a, i);
     uint64_t vpos;
     uint32_t vlen;
     bool walked;
-    if (get::table_get(T, k, &vpos, &vlen, &walked)) atomicMin(a.win + i, (uint32_t)t);
+    if (get::table_get(T, k, &vpos, &vlen, &walked)) atomicMin(a.win + i, (uint32_t)(a.base + t));
     if (a.count) {
       atomicAdd(a.info + 3, 1ull);
       if (walked) atomicAdd(a.info + 4, 1ull);
@@ -168,10 +148,10 @@ __global__ __launch_bounds__(256) void get_resolve(GetArgs a, lsmck_get_result* 
   const uint32_t t = a.win[i];
   lsmck_get_result r = get::result_none();
   if (t != get::kNoTable) {
-    const get::Table T = get_table(a, t);
+    const get::Table T = get::table_at(a, t);
     uint64_t vpos;
     uint32_t vlen;
-    if (get::table_get(T, get_key(a, i), &vpos, &vlen, nullptr))
+    if (get::table_get(T, get::key_at(a, i), &vpos, &vlen, nullptr))
       r = get::result_of(T.img, a.spans[t].data_off, vpos, vlen, t);
   }
   res[i] = r;
@@ -196,14 +176,21 @@ extern "C" int lsmk_get_index(const lsmck::GetArgs* a, hipStream_t st) {
   hipLaunchKernelGGL(get_items_keys, dim3(get_grid(a->nslots)), dim3(256), 0, st, *a);
   return get_launch_err();
 }
-extern "C" int lsmk_get_probe(const lsmck::GetArgs* a, hipStream_t st) {
+extern "C" int lsmk_get_queries(const lsmck::GetArgs* a, hipStream_t st) {
   hipLaunchKernelGGL(get_queries, dim3(get_grid(a->n)), dim3(256), 0, st, *a);
+  return get_launch_err();
+}
+extern "C" int lsmk_get_pairs(const lsmck::GetArgs* a, hipStream_t st) {
   if (a->ntab) {
     // at most 2^20 workgroups; the pairs beyond them by the grid's stride
     const uint64_t blocks = (a->n * a->ntab + 255u) / 256u;
     hipLaunchKernelGGL(get_probe, dim3((unsigned)(blocks < (1ull << 20) ? blocks : (1ull << 20))), dim3(256), 0, st, *a);
   }
   return get_launch_err();
+}
+extern "C" int lsmk_get_probe(const lsmck::GetArgs* a, hipStream_t st) {
+  const int rc = lsmk_get_queries(a, st);
+  return rc ? rc : lsmk_get_pairs(a, st);
 }
 extern "C" int lsmk_get_resolve(const lsmck::GetArgs* a, lsmck_get_result* res, hipStream_t st) {
   hipLaunchKernelGGL(get_resolve, dim3(get_grid(a->n)), dim3(256), 0, st, *a, res);

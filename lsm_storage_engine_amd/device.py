@@ -165,6 +165,22 @@ class SstGetError(_lib.LsmckError):
         super().__init__(rc, f"{what} (bad_table={bad_table}, bad_query={bad_query})")
 
 
+class DbGetError(_lib.LsmckError):
+    """lsmck_db_get_batch refused the batch: ``bad_run_entry`` is the first
+    offending run entry, counted across the runs, else ``bad_table`` the first
+    table refused, else ``bad_query`` the first query refused (LSMCK_EINVAL;
+    all None for an argument error); or ``needed`` the gathered values' bytes
+    when ``out`` holds fewer (LSMCK_ENOSPC)."""
+
+    def __init__(self, rc, what, bad_run_entry=None, bad_table=None, bad_query=None, needed=None):
+        self.bad_run_entry = bad_run_entry
+        self.bad_table = bad_table
+        self.bad_query = bad_query
+        self.needed = needed
+        super().__init__(rc, f"{what} (bad_run_entry={bad_run_entry}, bad_table={bad_table}, bad_query={bad_query}, "
+                             f"needed={needed})")
+
+
 class Context:
     def __init__(self, device=0):
         lib = _lib.load()
@@ -614,6 +630,84 @@ class Context:
         lsmck_get_result).  Raises SstGetError; nothing was written then."""
         self._sst_get(data_ptr, data_bytes, index_ptr, index_bytes, spans_ptr, ntab, qkeys_ptr, qkeys_bytes, queries_ptr,
                       n, res_ptr, _lib.DEVICE)
+
+    def _db_get(self, runs, data, db, index, ib, spans, ntab, qkeys, qb, q, n, res, out, out_cap, out_off, flags):
+        none = 2 ** 64 - 1
+        runs = np.ascontiguousarray(runs, dtype=_lib.GET_RUN_DTYPE)
+        br, bt, bq, nbytes = C.c_uint64(none), C.c_uint64(none), C.c_uint64(none), C.c_uint64(0)
+        rc = self.lib.lsmck_db_get_batch(self.handle, runs.ctypes.data if len(runs) else None, len(runs), data, db,
+                                         index, ib, spans, ntab, qkeys, qb, q, n, res, out, out_cap, out_off,
+                                         C.byref(nbytes), C.byref(br), C.byref(bt), C.byref(bq), flags)
+        if rc == _lib.EINVAL:
+            raise DbGetError(rc, "db_get_batch", *(None if w.value == none else w.value for w in (br, bt, bq)))
+        if rc == _lib.ENOSPC:
+            raise DbGetError(rc, "db_get_batch", needed=nbytes.value)
+        _lib.check(rc, "db_get_batch")
+        return nbytes.value
+
+    def db_get_batch(self, runs, data, index, spans, qkeys, queries, values=True, pinned=False):
+        """lsmck_db_get_batch, host form: Db::get of every query
+        (GET_QUERY_DTYPE over the uint8 arena ``qkeys``) over ``runs`` -- a
+        list of (keys, vals, ents): two uint8 arenas, which may be one array,
+        and WAL_CMD_DTYPE entries in strictly increasing key order; the
+        memtable first, then the old one -- and then the tables of
+        ``sstable_get_batch``.  Returns (res, out_off, out): GET_RESULT_DTYPE
+        per query (``table``: the source number, the runs first; ``val_off``
+        into the winning run's vals or ``data``), and with ``values`` the
+        exclusive scan of the answered lengths (np.uint64, n + 1) and the
+        values packed in that order (np.uint8) -- a tombstone or a miss has no
+        byte; both None without.  Raises DbGetError."""
+        keep, desc = [], np.zeros(len(runs), dtype=_lib.GET_RUN_DTYPE)
+        for r, (keys, vals, ents) in enumerate(runs):
+            keys = np.ascontiguousarray(keys, dtype=np.uint8)
+            vals = keys if vals is keys else np.ascontiguousarray(vals, dtype=np.uint8)
+            ents = np.ascontiguousarray(ents, dtype=_lib.WAL_CMD_DTYPE)
+            keep.append((keys, vals, ents))
+            desc[r] = (keys.ctypes.data if keys.nbytes else 0, keys.nbytes, vals.ctypes.data if vals.nbytes else 0,
+                       vals.nbytes, ents.ctypes.data if len(ents) else 0, len(ents))
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        index = np.ascontiguousarray(index, dtype=np.uint8)
+        spans = np.ascontiguousarray(spans, dtype=_lib.SSTABLE_SPAN_DTYPE)
+        qkeys = np.ascontiguousarray(qkeys, dtype=np.uint8)
+        queries = np.ascontiguousarray(queries, dtype=_lib.GET_QUERY_DTYPE)
+        n = len(queries)
+        res = np.empty(n, dtype=_lib.GET_RESULT_DTYPE)
+        flags = _lib.HOST_PINNED if pinned else _lib.HOST
+        args = (desc, _p(data), data.nbytes, _p(index), index.nbytes, _p(spans), len(spans), _p(qkeys), qkeys.nbytes,
+                _p(queries), n, _p(res))
+        if not values:
+            self._db_get(*args, None, 0, None, flags)
+            return res, None, None
+        off = np.empty(n + 1, dtype=np.uint64)
+        # a value is at most its source's bytes; a key asked twice is gathered twice, so the first size is a guess
+        out = np.empty(min(data.nbytes + sum(v.nbytes for _, v, _ in keep), 1 << 20), dtype=np.uint8)
+        try:
+            total = self._db_get(*args, _p(out), out.nbytes, off.ctypes.data, flags)
+        except DbGetError as e:
+            if e.needed is None:
+                raise
+            out = np.empty(e.needed, dtype=np.uint8)
+            total = self._db_get(*args, _p(out), out.nbytes, off.ctypes.data, flags)
+        return res, off, out[:total]
+
+    def db_get_batch_device(self, runs, data_ptr, data_bytes, index_ptr, index_bytes, spans_ptr, ntab, qkeys_ptr,
+                            qkeys_bytes, queries_ptr, n, res_ptr, out_ptr=None, out_cap=0, out_off_ptr=None):
+        """lsmck_db_get_batch on device pointers.  ``runs``: GET_RUN_DTYPE (a
+        host array of device pointers and sizes), or a list whose items are
+        such tuples (keys_ptr, keys_bytes, vals_ptr, vals_bytes, ents_ptr,
+        nent) or ``wal.DeviceMemTable``s (the image is both arenas).
+        ``out_off_ptr``: n + 1 u64 for the gather, or None for the results
+        alone.  Returns the gathered bytes; raises DbGetError (``needed``: the
+        bytes when out_cap is smaller); nothing was written then."""
+        if not isinstance(runs, np.ndarray):
+            desc = np.zeros(len(runs), dtype=_lib.GET_RUN_DTYPE)
+            for r, run in enumerate(runs):
+                if hasattr(run, "image_bytes"):
+                    run = (run.image.ptr, run.image_bytes, run.image.ptr, run.image_bytes, run.ents.ptr, run.nent)
+                desc[r] = tuple(0 if x is None else int(x) for x in run)
+            runs = desc
+        return self._db_get(runs, data_ptr, data_bytes, index_ptr, index_bytes, spans_ptr, ntab, qkeys_ptr, qkeys_bytes,
+                            queries_ptr, n, res_ptr, out_ptr, out_cap, out_off_ptr, _lib.DEVICE)
 
     def wal_recs_to_cmds_device(self, recs_ptr, n, img_bytes, cmds_ptr, stream=None):
         """lsmck_wal_recs_to_cmds: n compact replay records (lsmck_wal_rec16,
