@@ -291,7 +291,13 @@ int lsmck_device_count(void);
  *   "mem_build_time"  DIAGNOSTIC, not part of the stable option list, as
  *                 "wal_encode_time": 1 = lsmck_memtable_build records device
  *                 events around its stages (tools/memtable_big.py reads them
- *                 back as stats); 0 = none (default).
+ *                 back as stats); 0 = none (default).  It times
+ *                 lsmck_db_write_plan the same way (tools/write_big.py).
+ *   "cut_walk_cap"  lsmck_db_write_plan: the commands a candidate start's
+ *                 walk follows at most (default 4096, from 1); a memtable
+ *                 longer than that is found by one workgroup on the chain.
+ *   "cut_block"   lsmck_db_write_plan: the candidate starts one workgroup
+ *                 links in LDS, 4 bytes each (default 8192; 64..8192).
  * Returns 0, or LSMCK_EINVAL for an unknown key / value. */
 int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value);
 
@@ -370,6 +376,17 @@ int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value);
  *                    bytes, summed over the rounds; the rounds' fixed-width
  *                    part (sort passes, regroup, compaction), summed; resolve
  *                    and emit.
+ *   "cut_steps"      the walk steps of the last lsmck_db_write_plan, summed
+ *                    over the candidate starts (at most n * "cut_walk_cap");
+ *                    "cut_long" the memtables longer than "cut_walk_cap" that
+ *                    its chain resolved; "mem_rounds" is its order's rounds.
+ *   "write_order_ns", "write_walk_ns", "write_chain_ns", "write_mark_ns",
+ *   "write_emit_ns"  DIAGNOSTIC, subject to change: the last
+ *                    lsmck_db_write_plan's stages between device events, with
+ *                    "mem_build_time" 1: validation, the order's rounds and
+ *                    prev; the walk; the blocks' exits and the chain; the
+ *                    marks, the segment numbers and the entry flags; the sort
+ *                    by segment and the outputs.
  * Returns 0 and *value, or LSMCK_EINVAL for an unknown key. */
 int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value);
 
@@ -952,6 +969,77 @@ int lsmck_db_get_batch(lsmck_ctx* ctx, const lsmck_get_run* runs, size_t nrun, c
                        const uint8_t* qkeys, size_t qkeys_bytes, const lsmck_get_query* q, size_t n,
                        lsmck_get_result* res, uint8_t* out, size_t out_cap, uint64_t* out_off, uint64_t* out_bytes,
                        uint64_t* bad_run_entry, uint64_t* bad_table, uint64_t* bad_query, unsigned flags);
+
+/* Batch write plan: the batch form of the memtable side of LsmStorage::insert
+ * and LsmStorage::delete (src/sync/lsm_storage.rs:59-78, 133-139) -- where a
+ * command stream flushes, and what every flushed memtable holds.  Commands
+ * 0..n-1 (type 1 Insert, 2 delete; arenas and ranges as in
+ * lsmck_memtable_build, a delete's val_off and vlen are not looked at) are
+ * applied in order to an empty memtable, each as MemTable::insert
+ * (memtable.rs:72-79): an Insert puts (key, value), a delete puts (key, [0])
+ * (lsm_storage.rs:137), and size_in_bytes() stays the sum of klen + vlen over
+ * the pairs held -- an overwrite takes the pair it replaces away, unlike
+ * from_log's count.  After an Insert, and only then, size_in_bytes() >= limit
+ * flushes (lsm_storage.rs:65; >= as in the sync engine): the memtable ends
+ * with this command and the next command starts an empty one.  A delete never
+ * flushes, also when it takes the size past the limit; limit 0 flushes after
+ * every Insert.
+ * The result is *nflush closed segments and one open one, the memtable left
+ * (empty when the last command flushed): segs[0 .. *nflush] -- *nflush + 1
+ * items -- with segment g the commands [segs[g].first_cmd, segs[g+1].first_cmd)
+ * (n closes the last) and the entries [segs[g].first_ent, segs[g+1].first_ent)
+ * (*nent closes the last) of ents; segs[g].mem_bytes = size_in_bytes() at the
+ * segment's end.  A segment's entries are the last writer of every distinct
+ * key among its commands, in BTreeMap<Vec<u8>, _> order, as lsmck_wal_cmd of
+ * type 1, reserved 0, their ranges in the caller's arenas; a delete's entry
+ * has val_off = tomb_off and vlen = 1, and vals[tomb_off] must be a 0 byte the
+ * caller placed there (looked at only when the batch holds a delete).  The
+ * first_ent values of the closed segments are lsmck_sstable_encode_batch's
+ * table_first and ents its entries, unchanged.  src (optional): src[j] = the
+ * command ents[j] came from.
+ * Not modelled: a replayed memtable in front of the stream, the tokio
+ * engine's old_memtable, compact() behind a flush (lsm_storage.rs:74; it moves
+ * no cut), the bloom file, reads between the writes.
+ * On the device (lsmck_writeplan.hip, lsmck_writeplan.h): the memtable
+ * build's rounds order the commands by (key, log position); from that every
+ * command's predecessor with the same key.  A thread per candidate start
+ * walks its memtable for at most "cut_walk_cap" commands; the starts are cut
+ * into blocks of "cut_block", per block the orbits' exits are found by
+ * pointer doubling in LDS, one workgroup follows the true starts from block
+ * to block and resolves a start whose walk met the cap by windows of its
+ * width; a scan numbers the segments, a stable radix sort by segment number
+ * keeps key order inside each.
+ * flags: LSMCK_DEVICE -- keys, vals, cmds, ents, src and segs are device
+ * pointers, 8-byte aligned; LSMCK_HOST (optionally | LSMCK_HOST_PINNED, a hint
+ * only) -- host pointers, staged whole (the value arena is not: one byte of it
+ * is).  Any other flag bit is LSMCK_EINVAL.  nent, nflush and bad_index are
+ * host pointers either way (nent and nflush must not be NULL).  Synchronous;
+ * scratch comes from the context.  n >= 2^32 is LSMCK_EINVAL.
+ * Returns 0 (n == 0: one open segment {0, 0, 0}), or
+ *   LSMCK_EINVAL  with *bad_index = the first offending command: one
+ *                 lsmck_memtable_build refuses, or one whose entry would be
+ *                 too long for a table (8 + klen + vlen > 2^32-1); with
+ *                 *bad_index = UINT64_MAX: a delete is there and the
+ *                 tombstone byte lies past the arena or is not 0.
+ *   LSMCK_ENOSPC  ent_cap < *nent or seg_cap < *nflush + 1: both counts are
+ *                 the ones needed.
+ *   LSMCK_ENODEV  there is no GPU (and so no context).
+ * On any error no byte of ents, src or segs is written. */
+typedef struct { uint64_t first_cmd, first_ent, mem_bytes; } lsmck_write_seg;   /* 24 bytes */
+int lsmck_db_write_plan(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes, const uint8_t* vals, size_t vals_bytes,
+                        const lsmck_wal_cmd* cmds, size_t n, uint64_t limit, uint64_t tomb_off,
+                        lsmck_wal_cmd* ents, size_t ent_cap, uint32_t* src,
+                        lsmck_write_seg* segs, size_t seg_cap,
+                        size_t* nent, size_t* nflush, uint64_t* bad_index, unsigned flags);
+
+/* Host helper, no GPU: the same call on one thread with a std::map -- the
+ * scalar fallback, host pointers only.  The same results and errors (no
+ * LSMCK_ENODEV). */
+int lsmck_db_write_plan_cpu(const uint8_t* keys, size_t keys_bytes, const uint8_t* vals, size_t vals_bytes,
+                            const lsmck_wal_cmd* cmds, size_t n, uint64_t limit, uint64_t tomb_off,
+                            lsmck_wal_cmd* ents, size_t ent_cap, uint32_t* src,
+                            lsmck_write_seg* segs, size_t seg_cap,
+                            size_t* nent, size_t* nflush, uint64_t* bad_index);
 
 /* Whole-tree SSTable verify: the batch form of Checksums::verify over many
  * tables (Db::load, src/tokio/db.rs:37-59 -> src/tokio/sstable.rs:34).

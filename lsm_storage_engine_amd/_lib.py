@@ -103,6 +103,9 @@ GET_TOMBSTONE = 1 << 63  # LSMCK_GET_TOMBSTONE: bit 63 of lsmck_get_result.val_o
 GET_RUN_DTYPE = np.dtype([("keys", "<u8"), ("keys_bytes", "<u8"), ("vals", "<u8"), ("vals_bytes", "<u8"),
                           ("ents", "<u8"), ("nent", "<u8")])
 assert GET_RUN_DTYPE.itemsize == 48
+# include/lsmck.h lsmck_write_seg (24 bytes, no padding): one segment of lsmck_db_write_plan
+WRITE_SEG_DTYPE = np.dtype([("first_cmd", "<u8"), ("first_ent", "<u8"), ("mem_bytes", "<u8")])
+assert WRITE_SEG_DTYPE.itemsize == 24
 
 
 class TreeReport(C.Structure):
@@ -172,6 +175,11 @@ SIGNATURES = [
     ("lsmck_sstable_get", C.c_int, [vp, sz, vp, sz, vp, C.c_uint32, u64p, u32p]),
     ("lsmck_db_get_batch", C.c_int,  # runs: host lsmck_get_run[nrun]; out_off: u64[n + 1] or NULL; the last four: host
      [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, vp, sz, vp, u64p, u64p, u64p, u64p, C.c_uint]),
+    ("lsmck_db_write_plan", C.c_int,  # cmds: lsmck_wal_cmd[n]; ents, src: ent_cap; segs: lsmck_write_seg[seg_cap]
+     [vp, vp, sz, vp, sz, vp, sz, C.c_uint64, C.c_uint64, vp, sz, vp, vp, sz, C.POINTER(sz), C.POINTER(sz), u64p,
+      C.c_uint]),
+    ("lsmck_db_write_plan_cpu", C.c_int,  # the same call on the host, without context and flags
+     [vp, sz, vp, sz, vp, sz, C.c_uint64, C.c_uint64, vp, sz, vp, vp, sz, C.POINTER(sz), C.POINTER(sz), u64p]),
     ("lsmck_checksums_verify_many", C.c_int,
      [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), sz, C.POINTER(C.c_int)]),
     ("lsmck_tree_verify", C.c_int, [vp, C.c_char_p, C.POINTER(TreeReport)]),

@@ -423,6 +423,21 @@ struct lsmck_ctx {
   } mem;
   StageTimer mem_timer;  // "mem_build_time": validate, mem_chunk, the rounds' fixed-width part, resolve / emit
   long mem_rounds = 0;   // the last build's rounds
+  // batch write plan (lsmck_device.h WplWs, laid over mem.ws; mem.tmp, mem.ents
+  // and mem.src serve it too): the chain's entry points and the blocks' first
+  // ones, the call's words -- [0] the first command refused, [1] the tombstone
+  // byte is bad, [2] the walk steps, [3..6] the chain's four, [7] the entries,
+  // [8] the segments that hold a command -- and their pinned copy; host form:
+  // the tombstone byte and the segments
+  struct {
+    DevBuf<uint32_t> elist, bfirst;
+    DevBuf<unsigned long long> info;
+    PinBuf<unsigned long long> h_info;
+    DevBuf<uint8_t> tomb;
+    DevBuf<lsmck_write_seg> segs;
+  } wp;
+  StageTimer wp_timer;  // "mem_build_time" (this call too): order, walk, chain, mark, emit
+  long cut_steps = 0, cut_long = 0;  // the last plan's walk steps and LONG memtables
   // batch SSTable decode (lsmck_device.h DecArgs): the per-table and
   // per-segment scratch, the call's four words and their pinned copy; host
   // form: both images, the spans and the entries
@@ -1126,6 +1141,20 @@ int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value) {
     *value = ctx->mem_timer.ns[2];
   } else if (!strcmp(key, "mem_resolve_ns")) {
     *value = ctx->mem_timer.ns[3];
+  } else if (!strcmp(key, "cut_steps")) {  // the last lsmck_db_write_plan's walk steps
+    *value = ctx->cut_steps;
+  } else if (!strcmp(key, "cut_long")) {  // ... and the memtables its chain resolved
+    *value = ctx->cut_long;
+  } else if (!strcmp(key, "write_order_ns")) {  // the last timed plan's stages ("mem_build_time")
+    *value = ctx->wp_timer.ns[0];
+  } else if (!strcmp(key, "write_walk_ns")) {
+    *value = ctx->wp_timer.ns[1];
+  } else if (!strcmp(key, "write_chain_ns")) {
+    *value = ctx->wp_timer.ns[2];
+  } else if (!strcmp(key, "write_mark_ns")) {
+    *value = ctx->wp_timer.ns[3];
+  } else if (!strcmp(key, "write_emit_ns")) {
+    *value = ctx->wp_timer.ns[4];
   } else {
     return lsmck_host::set_error(LSMCK_EINVAL, "unknown stat");
   }
@@ -2575,6 +2604,170 @@ int lsmck_memtable_build(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes,
   }
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(T.span(5, 6, 3));
+  T.finish();
+  return 0;
+}
+
+int lsmck_db_write_plan(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes, const uint8_t* vals, size_t vals_bytes,
+                        const lsmck_wal_cmd* cmds, size_t n, uint64_t limit, uint64_t tomb_off, lsmck_wal_cmd* ents,
+                        size_t ent_cap, uint32_t* src, lsmck_write_seg* segs, size_t seg_cap, size_t* nent,
+                        size_t* nflush, uint64_t* bad_index, unsigned flags) {
+  if (nent) *nent = 0;
+  if (nflush) *nflush = 0;
+  if (bad_index) *bad_index = ~0ull;
+  if (!nent || !nflush) return lsmck_host::set_error(LSMCK_EINVAL, "write plan: null nent or nflush");
+  if (flags & ~(LSMCK_DEVICE | LSMCK_HOST_PINNED)) return lsmck_host::set_error(LSMCK_EINVAL, "write plan: unknown flag");
+  if (n >= (1ull << 32))
+    return lsmck_host::set_error(LSMCK_EINVAL, "write plan: more than 2^32-1 commands in one batch");
+  if (!ctx) return mem_no_ctx("write plan");
+  int rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DevGuard g(ctx->dev);
+  const hipStream_t st = ctx->stream0;
+  ScratchOrder so(ctx, st);
+  if (so.e != hipSuccess) return hip_error(so.e, "hipStreamWaitEvent(scratch)");
+  const bool dev = (flags & LSMCK_DEVICE) != 0;
+  if (n == 0) {  // the empty memtable, open
+    ctx->mem_rounds = ctx->cut_steps = ctx->cut_long = 0;
+    if (seg_cap < 1) return lsmck_host::set_error(LSMCK_ENOSPC, "write plan: seg_cap is smaller than the segments");
+    if (!segs) return lsmck_host::set_error(LSMCK_EINVAL, "null segs");
+    if (dev) {
+      HIPCHK(hipMemsetAsync(segs, 0, sizeof(lsmck_write_seg), st));
+      HIPCHK(hipStreamSynchronize(st));
+    } else {
+      memset(segs, 0, sizeof(lsmck_write_seg));
+    }
+    return 0;
+  }
+  if (!cmds) return lsmck_host::set_error(LSMCK_EINVAL, "null commands");
+  auto& M = ctx->mem;
+  auto& Q = ctx->wp;
+  const uint8_t *dk = keys, *dv = vals;
+  const lsmck_wal_cmd* dc = cmds;
+  // (no kernel reads a value but the tombstone byte: the value arena stays where it is)
+  if (!dev && (rc = stage_inputs(ctx, &dk, keys_bytes, &dv, vals_bytes, false, &dc, n, st))) return rc;
+  const uint8_t* tomb = nullptr;  // the tombstone byte on the device; null: it lies past the arena
+  if (vals && tomb_off < vals_bytes) {
+    tomb = vals + tomb_off;
+    if (!dev) {
+      if ((rc = Q.tomb.ensure(1))) return rc;
+      HIPCHK(hipMemcpyAsync(Q.tomb, vals + tomb_off, 1, hipMemcpyHostToDevice, st));
+      tomb = Q.tomb;
+    }
+  }
+  const uint32_t cap = (uint32_t)ctx->opt.cut_walk_cap, block = (uint32_t)ctx->opt.cut_block;
+  const uint64_t nblk = (n + block - 1) / block;
+  const uint32_t ecap = (uint32_t)std::min<uint64_t>({nblk + n / cap + 3, (uint64_t)n + 1, 0xFFFFFFFFull});
+  lsmck::MemWs W;
+  lsmck::WplWs P;
+  if ((rc = M.ws.ensure(lsmk_mem_carve(nullptr, n, nullptr))) || (rc = M.info.ensure(4)) ||
+      (rc = M.h_info.ensure(8, -1)) || (rc = Q.info.ensure(9)) || (rc = Q.h_info.ensure(16, -1)) ||
+      (rc = Q.elist.ensure(ecap)) || (rc = Q.bfirst.ensure((size_t)nblk)))
+    return rc;
+  (void)lsmk_mem_carve(M.ws, n, &W);
+  StageTimer& T = ctx->wp_timer;
+  T.begin(ctx->opt.mem_build_time);
+  // 1. validate; the words come back before any kernel reads a key
+  unsigned long long* info = Q.info;
+  HIPCHK(hipMemsetAsync(info, 0xFF, 8, st));
+  HIPCHK(hipMemsetAsync(info + 1, 0, 64, st));
+  HIPCHK(hipMemsetAsync(M.info + 1, 0, 8, st));
+  HIPCHK(T.mark(0, st));
+  if ((rc = lsmk_mem_validate(dc, n, keys_bytes, vals_bytes, info, st))) return launch_rc(rc, "write plan validate kernel");
+  if ((rc = lsmk_wpl_check(dc, n, tomb, info, st))) return launch_rc(rc, "write plan check kernel");
+  HIPCHK(hipMemcpyAsync(Q.h_info, info, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (Q.h_info[0] != ~0ull) {
+    if (bad_index) *bad_index = Q.h_info[0];
+    return lsmck_host::set_error(LSMCK_EINVAL, "write plan: invalid command (type, source range or an entry too long)");
+  }
+  if (Q.h_info[1])
+    return lsmck_host::set_error(LSMCK_EINVAL, "write plan: a delete needs a 0 byte at vals[tomb_off]");
+  // ... the order: the memtable build's rounds
+  if ((rc = lsmk_mem_init(&W, n, st))) return launch_rc(rc, "memtable init kernel");
+  unsigned group_bits = 1;
+  while (group_bits < 32 && ((uint64_t)1 << group_bits) < n) ++group_bits;
+  uint64_t m = n >= 2 ? n : 0;
+  long rounds = 0;
+  for (uint64_t r = 0; m; ++r, ++rounds) {
+    size_t tmp = 0;
+    if ((rc = lsmk_mem_sort_regroup(&W, m, r, group_bits, nullptr, &tmp, nullptr, st)))
+      return launch_rc(rc, "memtable sort (temporary storage size)");
+    if ((rc = M.tmp.ensure(tmp))) return rc;
+    if ((rc = lsmk_mem_chunk(&W, dk, dc, m, r, st))) return launch_rc(rc, "memtable chunk kernel");
+    tmp = M.tmp.cap();
+    if ((rc = lsmk_mem_sort_regroup(&W, m, r, group_bits, M.tmp, &tmp, M.info + 1, st)))
+      return launch_rc(rc, "memtable sort / regroup kernels");
+    HIPCHK(hipMemcpyAsync(M.h_info + 1, M.info + 1, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (M.h_info[1] > m) return lsmck_host::set_error(LSMCK_EIO, "write plan: active count grew");
+    m = M.h_info[1];
+    std::swap(W.apos, W.apos2);
+  }
+  ctx->mem_rounds = rounds;
+  lsmk_wpl_carve(&W, &P);
+  if ((rc = lsmk_wpl_prep(&P, dc, n, st))) return launch_rc(rc, "write plan prep kernel");
+  HIPCHK(T.mark(1, st));
+  // 2. the walk  3. the chain  4. the marks, the segment numbers, the entry flags
+  if ((rc = lsmk_wpl_walk(&P, n, limit, cap, info + 2, st))) return launch_rc(rc, "write plan walk kernel");
+  HIPCHK(T.mark(2, st));
+  if ((rc = lsmk_wpl_chain(&P, n, block, limit, Q.elist, ecap, Q.bfirst, info + 3, st)))
+    return launch_rc(rc, "write plan chain kernels");
+  HIPCHK(T.mark(3, st));
+  size_t tmp = 0;
+  if ((rc = lsmk_wpl_mark(&P, n, block, Q.elist, info + 3, Q.bfirst, nullptr, &tmp, st)))
+    return launch_rc(rc, "write plan scans (size)");
+  if ((rc = M.tmp.ensure(tmp))) return rc;
+  tmp = M.tmp.cap();
+  if ((rc = lsmk_wpl_mark(&P, n, block, Q.elist, info + 3, Q.bfirst, M.tmp, &tmp, st)))
+    return launch_rc(rc, "write plan mark kernels");
+  HIPCHK(T.mark(4, st));
+  // the one read-back: the steps, the chain's words, the entries, the segments
+  Q.h_info[7] = Q.h_info[8] = 0;
+  HIPCHK(hipMemcpyAsync(Q.h_info + 2, info + 2, 40, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(Q.h_info + 7, P.ex + n, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(Q.h_info + 8, P.seg1 + (n - 1), 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  ctx->cut_steps = (long)Q.h_info[2];
+  ctx->cut_long = (long)Q.h_info[4];
+  if (Q.h_info[6]) return lsmck_host::set_error(LSMCK_EIO, "write plan: the chain's entry list overflowed");
+  const int closed = Q.h_info[5] != 0;
+  const uint64_t live = Q.h_info[7], nseg = Q.h_info[8];
+  if (nseg == 0 || live < nseg) return lsmck_host::set_error(LSMCK_EIO, "write plan: no segment found");
+  const uint64_t flushes = closed ? nseg : nseg - 1;
+  *nent = (size_t)live;
+  *nflush = (size_t)flushes;
+  if (ent_cap < live || seg_cap < flushes + 1)
+    return lsmck_host::set_error(LSMCK_ENOSPC, "write plan: ent_cap or seg_cap is smaller than the result");
+  if (!ents || !segs) return lsmck_host::set_error(LSMCK_EINVAL, "null ents or segs");
+  lsmck_wal_cmd* de = ents;
+  uint32_t* ds = src;
+  lsmck_write_seg* dg = segs;
+  if (!dev) {
+    if ((rc = M.ents.ensure((size_t)live)) || (src && (rc = M.src.ensure((size_t)live))) ||
+        (rc = Q.segs.ensure((size_t)flushes + 1)))
+      return rc;
+    de = M.ents;
+    ds = src ? M.src.get() : nullptr;
+    dg = Q.segs;
+  }
+  tmp = 0;
+  if ((rc = lsmk_wpl_emit(&P, dc, n, live, nseg, closed, tomb_off, de, ds, dg, nullptr, &tmp, st)))
+    return launch_rc(rc, "write plan sort (temporary storage size)");
+  if ((rc = M.tmp.ensure(tmp))) return rc;
+  tmp = M.tmp.cap();
+  HIPCHK(T.mark(5, st));
+  if ((rc = lsmk_wpl_emit(&P, dc, n, live, nseg, closed, tomb_off, de, ds, dg, M.tmp, &tmp, st)))
+    return launch_rc(rc, "write plan emit kernels");
+  HIPCHK(T.mark(6, st));
+  if (!dev) {
+    HIPCHK(hipMemcpyAsync(ents, de, (size_t)live * sizeof(lsmck_wal_cmd), hipMemcpyDeviceToHost, st));
+    if (src) HIPCHK(hipMemcpyAsync(src, ds, (size_t)live * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(segs, dg, ((size_t)flushes + 1) * sizeof(lsmck_write_seg), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  const int pair[5][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {5, 6}};
+  for (int k = 0; k < 5; ++k) HIPCHK(T.span(pair[k][0], pair[k][1], k));
   T.finish();
   return 0;
 }

@@ -17,6 +17,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <map>
 #include <string>
 #include <vector>
 
@@ -24,6 +25,7 @@
 #include "lsmck_internal.h"
 #include "lsmck_sstget.h"
 #include "lsmck_sstmerge.h"
+#include "lsmck_writeplan.h"
 
 #if defined(__x86_64__)
 #include <cpuid.h>
@@ -522,6 +524,81 @@ int lsmck_sstable_get(const uint8_t* data, size_t data_len, const uint8_t* index
   if (!G::table_get(T, G::key_of(key, 0, klen), &vp, &vl, nullptr)) return 0;
   *val_off = vp, *vlen = vl;
   return 1;
+}
+
+// lsmck_db_write_plan on one thread: the literal loop of LsmStorage::insert /
+// delete (src/sync/lsm_storage.rs:59-78, 133-139) over a std::map in the
+// BTreeMap's order; the checks are lsmck_writeplan.h's, as on the device
+int lsmck_db_write_plan_cpu(const uint8_t* keys, size_t keys_bytes, const uint8_t* vals, size_t vals_bytes,
+                            const lsmck_wal_cmd* cmds, size_t n, uint64_t limit, uint64_t tomb_off,
+                            lsmck_wal_cmd* ents, size_t ent_cap, uint32_t* src, lsmck_write_seg* segs, size_t seg_cap,
+                            size_t* nent, size_t* nflush, uint64_t* bad_index) {
+  namespace W = lsmck::wpl;
+  if (nent) *nent = 0;
+  if (nflush) *nflush = 0;
+  if (bad_index) *bad_index = ~0ull;
+  if (!nent || !nflush) return lsmck_host::set_error(LSMCK_EINVAL, "write plan: null nent or nflush");
+  if (n >= (1ull << 32))
+    return lsmck_host::set_error(LSMCK_EINVAL, "write plan: more than 2^32-1 commands in one batch");
+  if (n && !cmds) return lsmck_host::set_error(LSMCK_EINVAL, "null commands");
+  bool deletes = false;
+  for (size_t i = 0; i < n; ++i) {
+    if (!lsmck::mem::valid(cmds[i], keys_bytes, vals_bytes) || !W::fits(cmds[i])) {
+      if (bad_index) *bad_index = i;
+      return lsmck_host::set_error(LSMCK_EINVAL, "write plan: invalid command (type, source range or an entry too long)");
+    }
+    deletes |= cmds[i].type == 2u;
+  }
+  if (deletes && (!vals || W::tomb_bad(vals, vals_bytes, tomb_off)))
+    return lsmck_host::set_error(LSMCK_EINVAL, "write plan: a delete needs a 0 byte at vals[tomb_off]");
+  struct Key {
+    const uint8_t* p;
+    uint32_t len;
+    bool operator<(const Key& o) const {
+      const uint32_t m = len < o.len ? len : o.len;
+      const int c = m ? memcmp(p, o.p, m) : 0;
+      return c ? c < 0 : len < o.len;
+    }
+  };
+  std::map<Key, uint32_t> table;  // the key's last writer in the current memtable
+  std::vector<uint32_t> order;    // the entries' commands, segment after segment
+  std::vector<lsmck_write_seg> sg;
+  uint64_t bytes = 0, first_cmd = 0;
+  auto close = [&](uint64_t next_cmd) {
+    lsmck_write_seg s;
+    s.first_cmd = first_cmd, s.first_ent = order.size(), s.mem_bytes = bytes;
+    sg.push_back(s);
+    for (const auto& kv : table) order.push_back(kv.second);
+    table.clear();
+    bytes = 0;
+    first_cmd = next_cmd;
+  };
+  for (size_t i = 0; i < n; ++i) {
+    const lsmck_wal_cmd& c = cmds[i];
+    const Key k{c.klen ? keys + c.key_off : nullptr, c.klen};
+    auto it = table.find(k);
+    if (it != table.end()) {  // MemTable::insert (memtable.rs:72-79): the pair replaced goes
+      bytes -= W::a_of(W::pack(cmds[it->second]));
+      it->second = (uint32_t)i;
+    } else {
+      table.emplace(k, (uint32_t)i);
+    }
+    bytes += W::a_of(W::pack(c));
+    if (c.type == 1u && bytes >= limit) close(i + 1);
+  }
+  const size_t flushes = sg.size();
+  close(n);  // the open segment
+  *nent = order.size();
+  *nflush = flushes;
+  if (ent_cap < order.size() || seg_cap < flushes + 1)
+    return lsmck_host::set_error(LSMCK_ENOSPC, "write plan: ent_cap or seg_cap is smaller than the result");
+  if ((order.size() && !ents) || !segs) return lsmck_host::set_error(LSMCK_EINVAL, "null ents or segs");
+  for (size_t j = 0; j < order.size(); ++j) {
+    ents[j] = W::entry(cmds[order[j]], tomb_off);
+    if (src) src[j] = order[j];
+  }
+  memcpy(segs, sg.data(), sg.size() * sizeof(lsmck_write_seg));
+  return 0;
 }
 
 void lsmck_gen_zipf_lengths(uint64_t seed, double s, int kmax, uint32_t lmin, size_t n, uint32_t* out) {

@@ -80,6 +80,21 @@ struct MemWs {
   uint8_t *tail, *head;
 };
 
+// The batch write plan's arrays (lsmck_writeplan.hip; lsmk_wpl_carve lays them
+// over a MemWs whose rounds are done).  perm / head: the build's order.  Per
+// command: aw (klen + vlen and the Insert bit), prev (the command before with
+// its key), mark (a memtable starts here), seg1 (its segment's number plus
+// one).  Per candidate start: nxt / byt / state (its walk's outcome, and the
+// chain's for a LONG start), exitp (the last start of its orbit inside its
+// block).  Per position of the order: act / ex (it is an entry; its slot;
+// n + 1).  Per entry: ekey / eval (segment and command in key order), skey /
+// sval (by segment, then key).
+struct WplWs {
+  uint64_t *aw, *byt;
+  uint32_t *perm, *prev, *nxt, *exitp, *mark, *seg1, *act, *ex, *ekey, *eval, *skey, *sval;
+  uint8_t *head, *state;
+};
+
 // The batch SSTable decode's arguments and scratch (lsmck_sstmerge.hip dec_*).
 // Per table: segfirst (its hint's items, then their exclusive scan: its place
 // in segpos; ntab + 1), state / fail (lsmck_sstmerge.hip kDec*; bit 0 of fail:
@@ -208,6 +223,21 @@ int lsmk_mem_emit(const lsmck::MemWs* W, const lsmck_wal_cmd* cmds, uint64_t n, 
                   hipStream_t st);
 int lsmk_mem_recs_to_cmds(const lsmck_wal_rec16* recs, uint64_t n, uint64_t img_bytes, lsmck_wal_cmd* cmds,
                           hipStream_t st);
+// batch write plan (lsmck_db_write_plan; lsmck_writeplan.hip wpl_*)
+void lsmk_wpl_carve(const lsmck::MemWs* W, lsmck::WplWs* P);
+int lsmk_wpl_check(const lsmck_wal_cmd* cmds, uint64_t n, const uint8_t* tomb, unsigned long long* info,
+                   hipStream_t st);
+int lsmk_wpl_prep(const lsmck::WplWs* P, const lsmck_wal_cmd* cmds, uint64_t n, hipStream_t st);
+int lsmk_wpl_walk(const lsmck::WplWs* P, uint64_t n, uint64_t limit, uint32_t cap, unsigned long long* steps,
+                  hipStream_t st);
+int lsmk_wpl_chain(const lsmck::WplWs* P, uint64_t n, uint32_t block, uint64_t limit, uint32_t* elist, uint32_t ecap,
+                   uint32_t* bfirst, unsigned long long* cinfo, hipStream_t st);
+int lsmk_wpl_mark(const lsmck::WplWs* P, uint64_t n, uint32_t block, const uint32_t* elist,
+                  const unsigned long long* cinfo, const uint32_t* bfirst, void* tmp, size_t* tmp_bytes,
+                  hipStream_t st);
+int lsmk_wpl_emit(const lsmck::WplWs* P, const lsmck_wal_cmd* cmds, uint64_t n, uint64_t nent, uint64_t nseg,
+                  int closed, uint64_t tomb_off, lsmck_wal_cmd* ents, uint32_t* src, lsmck_write_seg* segs, void* tmp,
+                  size_t* tmp_bytes, hipStream_t st);
 int lsmk_launch_crc32_fixed(const lsmck::CrcParams* P, int ncu, int variant, hipStream_t st);
 int lsmk_launch_sha256(const lsmck::ShaParams* P, hipStream_t st);
 int lsmk_launch_sha256_slices(const lsmck::ShaSliceParams* P, hipStream_t st);

@@ -37,6 +37,8 @@ struct Options {
   long sha_bucket_from = 128, sha_bucket_shift = 2, sha_short_blocks = 12, sha_pair = 1;
   // diagnostics: the batch builders' stages between device events
   long wal_encode_time = 0, sst_encode_time = 0, mem_build_time = 0;
+  // the batch write plan: a candidate start's walk steps at most, the starts a workgroup links in LDS
+  long cut_walk_cap = 4096, cut_block = 8192;
 };
 
 // `variant` bits
@@ -132,13 +134,21 @@ constexpr OptionRow kOptions[] = {
     LSMCK_OPT(sst_encode_time, 0, 1),
     LSMCK_OPT(mem_build_time, 0, 1),
 };
+// the batch write plan's rows (lsmck_db_write_plan), looked up behind kOptions
+constexpr OptionRow kPlanOptions[] = {
+    LSMCK_OPT(cut_walk_cap, 1, 1l << 30),
+    LSMCK_OPT(cut_block, 64, 8192),
+};
 #undef LSMCK_OPT
 
 // Looks `key` up, checks `value` against its row and stores it.  Returns 0, or
 // LSMCK_EINVAL with *why naming the key and the values it takes (nothing stored).
 inline int option_set(Options& o, const char* key, long value, const OptionEnv& env, std::string* why) {
   if (!key) return *why = "null key", LSMCK_EINVAL;
-  for (const OptionRow& r : kOptions) {
+  constexpr size_t kRows = sizeof kOptions / sizeof kOptions[0];
+  constexpr size_t kPlanRows = sizeof kPlanOptions / sizeof kPlanOptions[0];
+  for (size_t i = 0; i < kRows + kPlanRows; ++i) {
+    const OptionRow& r = i < kRows ? kOptions[i] : kPlanOptions[i - kRows];
     if (strcmp(key, r.name)) continue;
     if (r.accepts) {
       if (!r.accepts(r, value, env, why)) return LSMCK_EINVAL;

@@ -1,5 +1,6 @@
-"""The read side of the reference's ``Db`` (src/tokio/db.rs:144-189,
-src/sync/lsm_storage.rs:101) for many keys.
+"""The reference's ``Db`` for many keys and many commands: the read side
+(src/tokio/db.rs:144-189, src/sync/lsm_storage.rs:101) and the write side
+(src/sync/lsm_storage.rs:59-78, 133-139).
 
 ``Db::get_internal`` asks the memtable (db.rs:158-165), then the old memtable
 (db.rs:166-173), then every level's tables newest first (db.rs:178-185); the
@@ -9,7 +10,18 @@ what ``Db::delete`` inserts (db.rs:140) -- into ``None`` (db.rs:146-151).
 ``lsmck_db_get_batch`` call with one -- the memtables become sorted runs, the
 tables' files are uploaded once, and the values come back gathered in one
 arena.
+
+``LsmStorage::insert`` appends to the WAL, updates the memtable and flushes it
+to a level-0 table when ``size_in_bytes() >= memtable_limit_bytes``
+(lsm_storage.rs:65); ``delete`` inserts the value ``[0]`` and never flushes.
+``write_many`` is that loop over a command stream: literally without a
+context, and with one as a single ``lsmck_db_write_plan`` call -- the cuts and
+every flushed memtable's entries -- whose entries go to one
+``lsmck_sstable_encode_batch`` and whose last commands to one
+``lsmck_wal_encode_batch``, all on the device.
 """
+import time
+
 import numpy as np
 
 from . import _lib, sstable
@@ -85,4 +97,112 @@ def get_many(memtables, levels, keys, ctx=None, internal=False):
     return out
 
 
-__all__ = ["get_many", "run_arrays", "TOMBSTONE_HIT", "DELETED"]
+def _write_loop(base_path, commands, limit, stamps):
+    """LsmStorage::insert / delete, command by command (lsm_storage.rs:59-78, 133-139)."""
+    from . import wal
+    mt, log, metas = wal.MemTable(), wal.CommandLog.new_in_memory(), []
+    for c in commands:
+        if isinstance(c, wal.Insert):
+            log.insert(c.key, c.val)
+            mt.insert(c.key, c.val)
+            if mt.bytes >= limit:
+                metas.append(sstable.from_memtable(base_path, mt, ctx=None, timestamp_ms=stamps(len(metas))))
+                log = wal.CommandLog.new_in_memory()  # (wal.close() deletes the file, a new one is created)
+                mt = wal.MemTable()
+        else:
+            log.remove(c.key)
+            mt.insert(c.key, DELETED)
+    return metas, mt, log.inner()
+
+
+def write_many(base_path, commands, limit, ctx=None, timestamps_ms=None):
+    """LsmStorage::insert / delete for a stream of ``wal.Insert`` /
+    ``wal.Remove`` commands applied to a new, empty ``Db`` whose
+    memtable_limit_bytes is ``limit``: every flush becomes a level-0 table
+    under ``base_path`` (``timestamps_ms``: one per flush, in order).  Without
+    a context the literal loop runs -- ``wal.MemTable.insert``, a
+    ``CommandLog`` per memtable, ``sstable.from_memtable`` per flush; with one
+    the commands go up once, lsmck_db_write_plan cuts them and orders every
+    memtable, lsmck_sstable_encode_batch writes the flushed ones from its
+    entries on the device and lsmck_wal_encode_batch frames the commands
+    behind the last flush.  compact() behind a flush is the caller's
+    (``sstable.merge_compact_many``).  Returns (the level-0 SsTableMetadata in
+    flush order, the memtable left as a ``wal.MemTable`` -- a delete is the
+    value ``b"\\x00"`` --, the WAL image).  The files and both other results
+    are equal either way."""
+    from . import wal
+    from .device import SstEncodeError
+    commands = list(commands)
+    t0 = int(time.time() * 1000)
+
+    def stamps(i):
+        return t0 + i if timestamps_ms is None else timestamps_ms[i]
+    if ctx is None:
+        return _write_loop(str(base_path), commands, limit, stamps)
+    n = len(commands)
+    cmds, _ = wal.encode_commands(commands)
+    keys = np.frombuffer(b"".join(c.key for c in commands), dtype=np.uint8)
+    vals = np.frombuffer(b"".join(c.val for c in commands if isinstance(c, wal.Insert)) + DELETED, dtype=np.uint8)
+    tomb_off = len(vals) - 1  # the 0 byte a delete's entry points at
+    bufs = []
+
+    def dev(nbytes, src=None):
+        b = ctx.alloc(max(nbytes, 1))
+        bufs.append(b)
+        if src is not None and src.nbytes:
+            b.upload(src)
+        return b
+    try:
+        dk, dv, dc = dev(keys.nbytes, keys), dev(vals.nbytes, vals), dev(cmds.nbytes, cmds)
+        dents, dsegs = dev(32 * n), dev(24 * (n + 1))
+        nent, nflush = ctx.db_write_plan_device(dk.ptr, keys.nbytes, dv.ptr, vals.nbytes, dc.ptr, n, limit, tomb_off,
+                                                dents.ptr, n, None, dsegs.ptr, n + 1)
+        segs = dsegs.download(_lib.WRITE_SEG_DTYPE, nflush + 1)
+        first = segs["first_ent"].copy()  # the flushed tables' table_first
+        metas = []
+        if nflush:
+            args = (dk.ptr, keys.nbytes, dv.ptr, vals.nbytes, dents.ptr, int(first[nflush]), first)
+            try:  # the sizes: an index file holds its count at least, so no buffer at all is too small
+                ctx.sstable_encode_batch_device(*args, None, 0, None, 0)
+                raise AssertionError("an index file is never empty")
+            except SstEncodeError as e:
+                if e.needed is None:
+                    raise
+                db, ib = e.needed
+            data, index, dspans, sha = dev(db), dev(ib), dev(32 * nflush), dev(64 * nflush)
+            got = ctx.sstable_encode_batch_device(*args, data.ptr, db, index.ptr, ib, dspans.ptr, sha.ptr,
+                                                  sha.ptr + 32 * nflush)
+            assert got == (db, ib)
+            hd, hx = memoryview(data.download(np.uint8, db)), memoryview(index.download(np.uint8, ib))
+            spans = dspans.download(_lib.SSTABLE_SPAN_DTYPE, nflush)
+            digests = sha.download(np.uint8, 64 * nflush).reshape(2, nflush, 32)
+            for t in range(nflush):
+                sp = spans[t]
+                d0, i0 = int(sp["data_off"]), int(sp["index_off"])
+                m = sstable.SsTableMetadata.new(str(base_path), 0, timestamp_ms=stamps(t))
+                metas.append(sstable._write_table(m, hd[d0:d0 + int(sp["data_len"])], hx[i0:i0 + int(sp["index_len"])],
+                                                  digests[1][t], digests[0][t]))
+        # the memtable left and its commands' log
+        mt = wal.MemTable()
+        e0, c0 = int(first[nflush]), int(segs["first_cmd"][nflush])
+        ents = dents.download(_lib.WAL_CMD_DTYPE, nent - e0, 32 * e0)
+        kb, vb = keys.tobytes(), vals.tobytes()
+        for ko, kl, vo, vl in zip(ents["key_off"].tolist(), ents["klen"].tolist(), ents["val_off"].tolist(),
+                                  ents["vlen"].tolist()):
+            mt.data[kb[ko:ko + kl]] = vb[vo:vo + vl]
+        mt.bytes = int(segs["mem_bytes"][nflush])
+        image = b""
+        if c0 < n:
+            size = ctx.lib.lsmck_wal_encoded_size(cmds[c0:].ctypes.data, n - c0)
+            dimg = dev(size)
+            got = ctx.wal_encode_batch_device(dk.ptr, keys.nbytes, dv.ptr, vals.nbytes, dc.ptr + 32 * c0, n - c0,
+                                              dimg.ptr, size)
+            assert got == size
+            image = dimg.download(np.uint8, size).tobytes()
+        return metas, mt, image
+    finally:
+        for b in bufs:
+            b.free()
+
+
+__all__ = ["get_many", "run_arrays", "write_many", "TOMBSTONE_HIT", "DELETED"]

@@ -126,6 +126,18 @@ class MemBuildError(_lib.LsmckError):
         super().__init__(rc, f"{what} (bad_index={bad_index}, needed={needed})")
 
 
+class WritePlanError(_lib.LsmckError):
+    """lsmck_db_write_plan refused the batch: ``bad_index`` is the first
+    invalid command (LSMCK_EINVAL; None when the tombstone byte is missing or
+    an argument is wrong), or ``needed`` = (entries, flushes) when an array
+    given holds fewer (LSMCK_ENOSPC); the other one is None."""
+
+    def __init__(self, rc, what, bad_index=None, needed=None):
+        self.bad_index = bad_index
+        self.needed = needed
+        super().__init__(rc, f"{what} (bad_index={bad_index}, needed={needed})")
+
+
 class SstDecodeError(_lib.LsmckError):
     """lsmck_sstable_decode_batch refused the batch: ``bad_index`` is the first
     table whose span is refused (LSMCK_EINVAL; None for an argument error), or
@@ -708,6 +720,50 @@ class Context:
             runs = desc
         return self._db_get(runs, data_ptr, data_bytes, index_ptr, index_bytes, spans_ptr, ntab, qkeys_ptr, qkeys_bytes,
                             queries_ptr, n, res_ptr, out_ptr, out_cap, out_off_ptr, _lib.DEVICE)
+
+    def _write_plan(self, keys, kb, vals, vb, cmds, n, limit, tomb_off, ents, ent_cap, src, segs, seg_cap, flags):
+        none = 2 ** 64 - 1
+        nent, nflush, bad = C.c_size_t(), C.c_size_t(), C.c_uint64(none)
+        rc = self.lib.lsmck_db_write_plan(self.handle, keys, kb, vals, vb, cmds, n, limit, tomb_off, ents, ent_cap, src,
+                                          segs, seg_cap, C.byref(nent), C.byref(nflush), C.byref(bad), flags)
+        if rc == _lib.EINVAL:
+            raise WritePlanError(rc, "db_write_plan", bad_index=None if bad.value == none else bad.value)
+        if rc == _lib.ENOSPC:
+            raise WritePlanError(rc, "db_write_plan", needed=(nent.value, nflush.value))
+        _lib.check(rc, "db_write_plan")
+        return nent.value, nflush.value
+
+    def db_write_plan(self, keys, vals, cmds, limit, tomb_off, pinned=False):
+        """lsmck_db_write_plan, host form: where the command stream ``cmds``
+        (WAL_CMD_DTYPE in order, type 1 Insert / 2 delete: key / value ranges
+        in the uint8 arenas ``keys`` / ``vals``) flushes at ``limit`` bytes,
+        and every memtable's entries.  ``vals[tomb_off]`` is the 0 byte a
+        delete's entry points at.  Returns (ents: WAL_CMD_DTYPE, segment after
+        segment in key order; src: np.uint32, the command each came from;
+        segs: WRITE_SEG_DTYPE, nflush + 1 items, the last one the memtable
+        left).  Raises WritePlanError (``bad_index``: the first invalid
+        command, None for the tombstone byte)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint8)
+        vals = keys if vals is keys else np.ascontiguousarray(vals, dtype=np.uint8)
+        cmds = np.ascontiguousarray(cmds, dtype=_lib.WAL_CMD_DTYPE)
+        n = len(cmds)
+        ents = np.empty(n, dtype=_lib.WAL_CMD_DTYPE)  # (at most every command is an entry, and closes a segment)
+        src = np.empty(n, dtype=np.uint32)
+        segs = np.empty(n + 1, dtype=_lib.WRITE_SEG_DTYPE)
+        flags = _lib.HOST_PINNED if pinned else _lib.HOST
+        nent, nflush = self._write_plan(_p(keys), keys.nbytes, _p(vals), vals.nbytes, _p(cmds), n, limit, tomb_off,
+                                        ents.ctypes.data, n, src.ctypes.data, segs.ctypes.data, n + 1, flags)
+        return ents[:nent], src[:nent], segs[:nflush + 1]
+
+    def db_write_plan_device(self, keys_ptr, keys_bytes, vals_ptr, vals_bytes, cmds_ptr, n, limit, tomb_off, ents_ptr,
+                             ent_cap, src_ptr, segs_ptr, seg_cap):
+        """lsmck_db_write_plan on device pointers (cmds: n lsmck_wal_cmd; ents:
+        ent_cap lsmck_wal_cmd; src_ptr: ent_cap u32 or None; segs: seg_cap
+        lsmck_write_seg).  Returns (nent, nflush); raises WritePlanError with
+        ``bad_index`` or ``needed`` = (the entries, the flushes: one segment
+        fewer than segs must hold); nothing was written then."""
+        return self._write_plan(keys_ptr, keys_bytes, vals_ptr, vals_bytes, cmds_ptr, n, limit, tomb_off, ents_ptr,
+                                ent_cap, src_ptr, segs_ptr, seg_cap, _lib.DEVICE)
 
     def wal_recs_to_cmds_device(self, recs_ptr, n, img_bytes, cmds_ptr, stream=None):
         """lsmck_wal_recs_to_cmds: n compact replay records (lsmck_wal_rec16,
