@@ -49,14 +49,15 @@ struct Stream {
   std::string key(const lsmck_wal_cmd& c) const { return std::string((const char*)keys + c.key_off, c.klen); }
 };
 
-// n commands over `distinct` keys of 0..5 bytes from two letters, values of 0..vmax bytes, one in `del_in` a delete
-static void make(Stream& s, size_t n, size_t distinct, uint32_t vmax, unsigned del_in) {
+// n commands over `distinct` keys of 0..5 bytes from `letters` letters, values of 0..vmax bytes, one in `del_in` a
+// delete
+static void make(Stream& s, size_t n, size_t distinct, uint32_t vmax, unsigned del_in, unsigned letters = 2) {
   std::vector<uint32_t> koff(distinct), klen(distinct);
   std::string karena;
   for (size_t d = 0; d < distinct; ++d) {
     koff[d] = (uint32_t)karena.size();
     klen[d] = (uint32_t)rnd(6);
-    for (uint32_t j = 0; j < klen[d]; ++j) karena.push_back((char)('a' + rnd(2)));
+    for (uint32_t j = 0; j < klen[d]; ++j) karena.push_back((char)('a' + rnd(letters)));
   }
   s.kb = karena.size();
   s.keys = (uint8_t*)malloc(s.kb ? s.kb : 1);
@@ -322,6 +323,33 @@ int main() {
     Stream one;
     make(one, 150, 1, 12, 5);
     for (uint64_t limit : limits) compare(one, limit, 4, 8, 3), ++runs;
+  }
+  // memtables longer than two windows at the kernels' window (1024) and at 1000, in blocks of the widths the GPU
+  // tests use: over a thousand keys, a limit that the first memtable reaches behind command 2100
+  for (size_t n : {2500, 3100}) {
+    Stream s;
+    make(s, n, 1200, 12, 6, 26);
+    uint64_t limit = 0;
+    {
+      std::map<std::string, uint64_t> mt;
+      uint64_t bytes = 0;
+      for (size_t i = 0; i <= 2100; ++i) {
+        const lsmck_wal_cmd& c = s.cmds[i];
+        const uint64_t a = (uint64_t)c.klen + wpl::ent_vlen(c);
+        auto it = mt.find(s.key(c));
+        if (it != mt.end()) bytes -= it->second;
+        mt[s.key(c)] = a, bytes += a;
+        limit = std::max(limit, bytes);
+      }
+    }
+    const Result want = reference(s, limit, 64);
+    g_what = "n " + std::to_string(n) + " limit " + std::to_string(limit);
+    // the first memtable is closed in its third window
+    CHECK(want.segs.size() >= 2 && want.segs[1].first_cmd > 2 * 1024 && want.nlong >= 1);
+    for (uint64_t lim : {limit, (uint64_t)~0ull})
+      for (uint32_t width : {1000u, 1024u})
+        for (uint32_t B : {1024u, 1025u, 8192u})
+          for (uint32_t cap : {4u, 64u, 4096u}) compare(s, lim, cap, B, width), ++runs;
   }
   printf("writeplan ok (%zu)\n", runs);
   return 0;

@@ -4,9 +4,12 @@ tests/test_write_cases.py proves on the CPU): the segments, the entries as (key
 bytes, value bytes) through the arenas, src, nent, nflush and the LONG count;
 the three outputs between 0xAA guards that must stay intact, as must
 everything past the counts.  The streams run with cut_block 64 and the
-stream's cut_walk_cap, so that a few hundred commands reach the blocks' and
-the cap's edges.  Then the host form, and db.write_many against the literal
-loop's files."""
+stream's cut_walk_cap (4, 64 or the default 4096), so that a few hundred
+commands reach the blocks' and the cap's edges; one case of 377 commands and
+the pipeline run at the default cut_block 8192.  Blocks of up to 8192
+starts, block widths that are no power of two and LONG memtables of more than
+one of the chain's windows are test_gpu_write_plan_wide.py's.  Then the host
+form, and db.write_many against the literal loop's files."""
 import filecmp
 import os
 

@@ -2,8 +2,8 @@
 leaves its outputs defined, the arguments that are checked before any GPU work
 are refused with or without one, and the binding names the call.  Then the
 host helper lsmck_db_write_plan_cpu -- the scalar fallback -- against the
-cases' restatement (write_cases.plan) on every small stream, its errors
-included.  No GPU compute call is made here."""
+cases' restatement (write_cases.plan) on every stream but the 2^18-command
+one, the window and wide-block streams among them, its errors included.  No GPU compute call is made here."""
 import ctypes as C
 
 import numpy as np
@@ -106,8 +106,8 @@ def check_cpu(s):
     assert untouched(ents[e:], src[e:], segs[k:])
 
 
-@pytest.mark.parametrize("s", Wc.smallest() + Wc.rule() + Wc.placement() + [Wc.sized(n, Wc.CAP) for n in (63, 1025)],
-                         ids=lambda s: s.name)
+@pytest.mark.parametrize("s", Wc.smallest() + Wc.rule() + Wc.placement() + [Wc.sized(n, Wc.CAP) for n in (63, 1025)] +
+                         Wc.windows() + Wc.wide(), ids=lambda s: s.name)
 def test_cpu_helper_equals_the_restatement(s):
     check_cpu(s)
 

@@ -4,8 +4,10 @@ delta and flush test, the entry predicate and the entry itself -- the code the
 kernels of lsmck_writeplan.hip run) as a host model under AddressSanitizer and
 UBSan (host code only; g++, a stand-alone program):
 tests/native/test_writeplan.cpp runs every step in the kernels' order, with
-caps, block sizes and window widths from 1 up, and compares with the literal
-loop over a std::map, the arenas exact-size blocks."""
+caps, block sizes and window widths from 1 up -- and 2500 and 3100 commands
+with windows of 1000 and 1024 in blocks of 1024, 1025 and 8192, memtables of
+more than two windows --, and compares with the literal loop over a std::map,
+the arenas exact-size blocks."""
 import os
 import subprocess
 

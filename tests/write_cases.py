@@ -1,5 +1,5 @@
 """Command streams for the batch write plan's tests (test_gpu_write_plan.py,
-test_write_abi.py).
+test_gpu_write_plan_wide.py, test_write_abi.py).
 
 lsmck_db_write_plan cuts a stream of Insert / delete commands where
 LsmStorage::insert would flush (src/sync/lsm_storage.rs:59-78, 133-139) and
@@ -14,6 +14,9 @@ delete's entry points at (``tomb_off``), a limit, and the two options the GPU
 tests set so that a few hundred commands reach the kernels' edges:
 ``cut_block`` (the starts a workgroup links) and ``cut_walk_cap`` (a start's
 walk steps at most; a longer memtable is LONG and found on the chain).
+``windows`` and ``wide`` are the streams of thousands of commands that the
+default options' paths need: LONG memtables of more than one of the chain's
+windows, and more than two blocks of 8192 starts.
 
 Nothing in this module needs a GPU: tests/test_write_cases.py checks that the
 streams reach the edges they claim.
@@ -73,6 +76,17 @@ def plan(records, limit):
             mt.insert(r.key, DELETED)
     close(len(records))
     return Plan(segs, entries, src, len(records))
+
+
+def bytes_trace(records, start):
+    """size_in_bytes() after each of ``records[start:]`` of a memtable that is
+    empty before command ``start`` and never flushed: [bytes(start, start),
+    bytes(start, start + 1), ...]."""
+    mt, out = wal.MemTable(), []
+    for r in records[start:]:
+        mt.insert(r.key, r.val if isinstance(r, wal.Insert) else DELETED)
+        out.append(mt.bytes)
+    return out
 
 
 class Stream:
@@ -157,7 +171,7 @@ def rule():
 T = 2000  # the placement streams' limit
 
 
-def by_lengths(name, lens, tail=0, **kw):
+def by_lengths(name, lens, tail=0, T=T, **kw):
     """Closed segments of exactly ``lens`` commands and ``tail`` open commands:
     Inserts of distinct 4-byte keys, a = 5 each but a segment's last, which
     brings bytes to the limit T exactly."""
@@ -201,7 +215,114 @@ def sized(n, cap):
     return Stream(f"sized_{n}/{cap}", M.sized(n), 64, cap=cap)
 
 
+# --- the chain's windows ----------------------------------------------------------------------
+W = 1024  # the chain's window: a LONG memtable is resolved W commands at a time
+WINDOW_LENGTHS = (1023, 1024, 1025, 1026, 2047, 2048, 2049, 3073)
+TW = 20000  # the window streams' limit
+E = 3  # the LONG start of every window stream: a closed segment of 3 commands lies before it
+OVERWRITES_LIMIT, OVERWRITES_CUT = 10200, E + 2252
+NEGATIVE_LIMIT, NEGATIVE_CUT = 9200, E + 2300
+LONG_RANDOM_LIMIT = 24 << 10
+
+
+def window_overwrites():
+    """One LONG memtable from command E whose bytes fall and rise: fills of
+    a = 4 (a 4-byte key, no value) around
+      E + 10    b"BIG." gets a value of 4996 bytes (a = 5000)
+      E + 20    b"LRG." gets a value of 1000 bytes (a = 1004)
+      E + 1030  b"BIG." is overwritten by an empty value: window 1's running total
+                is negative from here to its last lane but one
+      E + 1500  b"PREV", first written by command 1 (prev < E: nothing to subtract)
+      E + 2047  a delete of a new key of 1200 bytes, the last lane of window 1:
+                bytes passes the limit here, and a delete does not flush
+      E + 2048  b"LRG." is overwritten by an empty value: bytes is under the limit again
+      E + 2252  the first Insert at which bytes >= limit: the cut, in window 2
+    and five commands behind the cut, b"BIG." among them (its prev lies in the
+    memtable before).  (bytes passes the limit inside window 1, so that
+    window's whole total cannot be negative here: window_negative_total's is.)"""
+    special = {10: I(b"BIG.", b"b" * 4996), 20: I(b"LRG.", b"l" * 1000), 1030: I(b"BIG.", b""), 1500: I(b"PREV", b"q"),
+               2047: R(b"D" * 1200), 2048: I(b"LRG.", b"")}
+    return _long_from_e(special, OVERWRITES_LIMIT, OVERWRITES_CUT)
+
+
+def window_negative_total():
+    """The same without the delete and b"LRG.": window 1's total is -904, the
+    carry into window 2 is smaller than the carry into window 1, and the cut
+    is command E + 2300 in window 2."""
+    return _long_from_e({10: I(b"BIG.", b"b" * 4996), 1030: I(b"BIG.", b"")}, NEGATIVE_LIMIT, NEGATIVE_CUT)
+
+
+def _long_from_e(special, limit, cut):
+    """A closed segment of E commands, then fills of a = 4 with ``special``
+    (by distance from E) among them up to command ``cut``, five commands behind."""
+    fills = iter(range(1 << 20))
+
+    def fill():
+        return I(b"f" + next(fills).to_bytes(3, "big"), b"")
+    recs = [fill(), I(b"PREV", b"p"), I(b"k2..", b"x" * limit)]
+    recs += [special.get(j) or fill() for j in range(cut - E + 1)]
+    recs += [fill(), I(b"BIG.", b"zz"), R(b"PREV"), fill(), fill()]
+    return recs
+
+
+def windows():
+    """LONG memtables longer than the chain's window, each at cap 4 and at cap 64 with blocks of 64."""
+    out = []
+    for cap in (CAP_SMALL, CAP):
+        # the cut on the last lane of a window, the first of the next, one and three windows on
+        out += [by_lengths(f"long_len_{ln}/{cap}", [E, ln, 5, 2], tail=3, T=TW, cap=cap) for ln in WINDOW_LENGTHS]
+        # three LONG memtables one behind the other, the open one ends inside its second window
+        out.append(by_lengths(f"long_back_to_back/{cap}", [E, 1500, 1024, 2049], tail=1100, T=TW, cap=cap))
+        # the cut is found in window 1 on command n - 1
+        out.append(by_lengths(f"long_cut_on_last/{cap}", [E, 1030], T=TW, cap=cap))
+        out.append(stream(f"window_overwrites/{cap}", window_overwrites(), OVERWRITES_LIMIT, cap=cap))
+        out.append(stream(f"window_negative_total/{cap}", window_negative_total(), NEGATIVE_LIMIT, cap=cap))
+        # 2000 keys hold about 28 KiB when all are live: memtables of one to four windows
+        out.append(Stream(f"long_random/{cap}", M.random_log(20000, 2000, 4242, remove_one_in=16), LONG_RANDOM_LIMIT,
+                          cap=cap))
+    return out
+
+
+# --- wide blocks ------------------------------------------------------------------------------------
+WIDE_N = 2 * DEFAULT_BLOCK + 77
+WIDE_BLOCKS = (8192, 8191, 4097, 2048, 1025, 1024, 1000, 65)
+COVER_START, COVER_LEN = 100, 2 * DEFAULT_BLOCK + 200
+ENTRIES_N = DEFAULT_BLOCK + 100
+
+
+def straddle(d, cap):
+    """Segments of 50 commands up to command 7999, then one that ends on
+    command DEFAULT_BLOCK + d, short ones behind it into the third block."""
+    ln = DEFAULT_BLOCK + d + 1 - 8000
+    return by_lengths(f"straddle_{d:+d}/{cap}" if d else f"straddle_0/{cap}", [50] * 160 + [ln, 3, 5] + [50] * 165,
+                      tail=30, cap=cap, block=DEFAULT_BLOCK)
+
+
+def wide():
+    """Streams of more than two default blocks, each with its block and cap (the
+    GPU tests run them at every block width of WIDE_BLOCKS)."""
+    B = DEFAULT_BLOCK
+    ones = [I(i.to_bytes(4, "big"), bytes([i & 0xFF])) for i in range(WIDE_N)]
+    out = [stream("hops_ones", ones, 0, cap=DEFAULT_CAP, block=B)]  # a block's orbit is 8192 hops
+    for cap in (DEFAULT_CAP, CAP):
+        s = sized(WIDE_N, cap)
+        s.name, s.block = f"hops_mixed/{cap}", B
+        out.append(s)
+    for cap in (DEFAULT_CAP, CAP):
+        out += [straddle(d, cap) for d in (-1, 0, 1)]
+    # one memtable over all of block 1: LONG with 17 windows, or a cut whose nxt lies two blocks on
+    for cap in (DEFAULT_CAP, 4 * B):
+        out.append(by_lengths(f"covers_a_block/{cap}", [COVER_START, COVER_LEN, 5, 3, 7], tail=20, T=100000, cap=cap,
+                              block=B))
+    out.append(by_lengths("around_cap_4096", [4095, 4096, 4097, 5, 4096, 4098], tail=4096, T=40000, cap=DEFAULT_CAP,
+                          block=B))
+    # every memtable is LONG: thousands of chain entries in block 0
+    out.append(by_lengths("many_entries_in_block", [2, 3] * (ENTRIES_N // 5), tail=ENTRIES_N % 5, T=64, cap=1, block=B))
+    return out
+
+
 BIG_LIMITS = (0, 1, 64, 4096, 1 << 20, U64_MAX)
+BIG_WINDOW_LIMIT = 32 << 10  # closed memtables of two and three of the chain's windows
 _big = {}
 
 
