@@ -298,6 +298,10 @@ int lsmck_device_count(void);
  *                 longer than that is found by one workgroup on the chain.
  *   "cut_block"   lsmck_db_write_plan: the candidate starts one workgroup
  *                 links in LDS, 4 bytes each (default 8192; 64..8192).
+ *   "fence_walk_cap"  lsmck_tableset_open: the records a fence's walk visits
+ *                 at most (default 256, 1..2^20; INDEX_STEP is 100 and an
+ *                 interval with one item missing 200).  Read when a set is
+ *                 opened; a longer head or tail leaves that fence invalid.
  * Returns 0, or LSMCK_EINVAL for an unknown key / value. */
 int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value);
 
@@ -857,9 +861,10 @@ int lsmck_sstable_merge_batch(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_b
  * headers, and lowers the query's winning table with an atomic minimum; a
  * thread per query repeats the lookup in the winning table and writes res.
  * Db::get's memtable and old-memtable step in front of these tables, and the
- * values' bytes in one arena: lsmck_db_get_batch below.  Not covered: a
- * resident "opened table" form that keeps the index pass between calls, and
- * sorting queries by interval so that one walk serves many.
+ * values' bytes in one arena: lsmck_db_get_batch below.  A resident "opened
+ * table" form that keeps the index pass between calls: lsmck_tableset_open
+ * below.  Not covered: sorting queries by interval so that one walk serves
+ * many.
  * flags: LSMCK_DEVICE -- data, index, spans, qkeys, q (8-byte aligned) and res
  * are device pointers; LSMCK_HOST (optionally | LSMCK_HOST_PINNED, a hint
  * only) -- host pointers, staged whole.  Any other flag bit is LSMCK_EINVAL.
@@ -969,6 +974,71 @@ int lsmck_db_get_batch(lsmck_ctx* ctx, const lsmck_get_run* runs, size_t nrun, c
                        const uint8_t* qkeys, size_t qkeys_bytes, const lsmck_get_query* q, size_t n,
                        lsmck_get_result* res, uint8_t* out, size_t out_cap, uint64_t* out_off, uint64_t* out_bytes,
                        uint64_t* bad_run_entry, uint64_t* bad_table, uint64_t* bad_query, unsigned flags);
+
+/* Opened table set: SsTable::load (src/tokio/sstable.rs:32-55) for many tables
+ * once, then Db::get (src/tokio/db.rs:156-189) over them call after call -- a
+ * reader loads its tables once and serves gets until a compaction replaces
+ * them.  lsmck_tableset_open runs lsmck_sstable_get_batch's index pass once
+ * and keeps what it proves (spans, per item the order key, offset and
+ * position) in buffers the set owns, never in the context's scratch; and it
+ * computes per table two KEY FENCES.  With items (key_j, pos_j), j < m, and
+ * data length L (m == 0: no fence):
+ *   low   the walk of scan_range(0, pos_0): the record at 0 is attempted even
+ *         when pos_0 is 0, then the walk goes on while pos < pos_0 and a whole
+ *         record fits.  Valid when it ends within "fence_walk_cap" records and
+ *         no visited key is below key_0: then every k < key_0 is None.
+ *   high  the walk of scan_range(pos_{m-1}, L) by the same rule.  Valid when it
+ *         ends within the cap; hi = max(key_{m-1}, the visited keys): then
+ *         every k > hi is None.
+ * Both follow from the literal SsTable::get alone (lsmck_tableset.h has the
+ * argument), for positions that are any u64, records that hold any key, and
+ * tails that are unsorted or cut: a fenced (query, table) pair costs two key
+ * compares and no lookup, and no result differs.
+ * open (tokio/sstable.rs:32-55).  The rules, the refusals, the first
+ * bad_table and the cases checked before any GPU work are
+ * lsmck_sstable_get_batch's, word for word.  flags: LSMCK_DEVICE -- data,
+ * index and spans are device pointers and the set BORROWS data and index: the
+ * caller keeps them alive and unchanged until lsmck_tableset_close (item keys
+ * that tie past 8 bytes still read index bytes; spans is copied); LSMCK_HOST
+ * (optionally | LSMCK_HOST_PINNED) -- host pointers, and the set OWNS device
+ * copies, staged once: the caller's arrays are free after return.  ntab == 0
+ * is a valid set.  On any error *set = NULL and nothing is retained.  `set`
+ * and bad_table (may be NULL) are host pointers.
+ * get (tokio/db.rs:156-189).  lsmck_db_get_batch with the set in place of
+ * (data, index, spans): meaning, result encoding (val_off relative to the
+ * arena the set was opened over), gather, error order and "no byte written on
+ * error" are that call's word for word, but that no table can be refused any
+ * more.  `flags` describe the per-call pointers alone -- the run descriptors'
+ * pointers, qkeys, q, res, out, out_off -- host or device whichever way the
+ * set was opened.  A set used with a context other than the one that opened
+ * it, or a NULL set, is LSMCK_EINVAL.  On the device (lsmck_tableset.hip): the
+ * kernels of lsmck_db_get_batch without the index pass, and a table probe
+ * that tests the fences before it looks anything up.
+ * stat.  "tables", "items" (index items of all tables), "fenced_low" and
+ * "fenced_high" (the tables with each fence), "resident_bytes" (device bytes
+ * the set owns).  LSMCK_EINVAL for an unknown key or a NULL argument.
+ * close.  Frees the set; NULL is a no-op.  Sets are closed before their
+ * context is destroyed.
+ * With "sst_encode_time" 1, lsmck_ctx_get_stat has "tableset_open_index_ns" and
+ * "tableset_open_fence_ns" for the last open, and for the last get
+ * "tableset_runs_ns", "tableset_run_probe_ns", "tableset_probe_ns",
+ * "tableset_resolve_ns", "tableset_gather_ns", and "tableset_probed" /
+ * "tableset_walked" / "tableset_fenced": the (query, table) pairs looked up,
+ * those whose interval was walked, and those the fences dropped (counted
+ * before the check for a lower source's answer, so a fixed number per input).
+ * Not covered: an opened run form, sorting queries by interval, a
+ * host-resident opened table for the scalar lsmck_sstable_get, fences for a
+ * table without index items, the bloom file. */
+typedef struct lsmck_tableset lsmck_tableset;
+int lsmck_tableset_open(lsmck_ctx* ctx, const uint8_t* data, size_t data_bytes, const uint8_t* index,
+                        size_t index_bytes, const lsmck_sstable_span* spans, size_t ntab, lsmck_tableset** set,
+                        uint64_t* bad_table, unsigned flags);
+int lsmck_tableset_get_batch(lsmck_ctx* ctx, const lsmck_tableset* set, const lsmck_get_run* runs, size_t nrun,
+                             const uint8_t* qkeys, size_t qkeys_bytes, const lsmck_get_query* q, size_t n,
+                             lsmck_get_result* res, uint8_t* out, size_t out_cap, uint64_t* out_off,
+                             uint64_t* out_bytes, uint64_t* bad_run_entry, uint64_t* bad_query, unsigned flags);
+int lsmck_tableset_stat(const lsmck_tableset* set, const char* key, long* value);
+void lsmck_tableset_close(lsmck_tableset* set);
 
 /* Batch write plan: the batch form of the memtable side of LsmStorage::insert
  * and LsmStorage::delete (src/sync/lsm_storage.rs:59-78, 133-139) -- where a

@@ -175,6 +175,12 @@ SIGNATURES = [
     ("lsmck_sstable_get", C.c_int, [vp, sz, vp, sz, vp, C.c_uint32, u64p, u32p]),
     ("lsmck_db_get_batch", C.c_int,  # runs: host lsmck_get_run[nrun]; out_off: u64[n + 1] or NULL; the last four: host
      [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, vp, vp, sz, vp, u64p, u64p, u64p, u64p, C.c_uint]),
+    ("lsmck_tableset_open", C.c_int,  # set: host lsmck_tableset*; bad_table: host
+     [vp, vp, sz, vp, sz, vp, sz, C.POINTER(vp), u64p, C.c_uint]),
+    ("lsmck_tableset_get_batch", C.c_int,  # lsmck_db_get_batch with the set in place of data, index and spans
+     [vp, vp, vp, sz, vp, sz, vp, sz, vp, vp, sz, vp, u64p, u64p, u64p, C.c_uint]),
+    ("lsmck_tableset_stat", C.c_int, [vp, C.c_char_p, C.POINTER(C.c_long)]),
+    ("lsmck_tableset_close", None, [vp]),
     ("lsmck_db_write_plan", C.c_int,  # cmds: lsmck_wal_cmd[n]; ents, src: ent_cap; segs: lsmck_write_seg[seg_cap]
      [vp, vp, sz, vp, sz, vp, sz, C.c_uint64, C.c_uint64, vp, sz, vp, vp, sz, C.POINTER(sz), C.POINTER(sz), u64p,
       C.c_uint]),

@@ -45,6 +45,7 @@
 #include "lsmck_pool.h"
 #include "lsmck_segwalk.h"
 #include "lsmck_sstmerge.h"
+#include "lsmck_tableset.h"
 
 using lsmck::CrcParams;
 using lsmck::ShaParams;
@@ -504,6 +505,13 @@ struct lsmck_ctx {
   long dbg_probed = 0;   // the last timed call's (query, table) pairs looked up
   long dbg_walked = 0;   // ... whose interval was walked
   long dbg_run_hits = 0;  // ... and its queries a run answered
+  // opened table sets (lsmck_tableset below): the tables' arrays live in the
+  // set; a get's per-query scratch is `get` and `dbg` above
+  StageTimer ts_open_timer;  // "sst_encode_time" (lsmck_tableset_open): index pass, fences
+  StageTimer ts_timer;       // ... (lsmck_tableset_get_batch): dbg_timer's stages, the index pass's always 0
+  long ts_probed = 0;        // the last timed get's (query, table) pairs looked up
+  long ts_walked = 0;        // ... whose interval was walked
+  long ts_fenced = 0;        // ... and those the fences dropped
   bool wal_recs_direct = false;  // this replay's records go by DMA into the caller's pinned array (under wal_mu)
   bool wal_compact = false;      // this replay's records are lsmck_wal_rec16 (under wal_mu)
   // LSMCK_RECS_DEVICE (under wal_mu): the caller's device array and its capacity
@@ -562,6 +570,28 @@ struct lsmck_ctx {
     DevBuf<unsigned char> digests;   // 32 B per file of the call
     hipEvent_t kernel_done = nullptr;
   } tree;
+};
+
+// An opened table set: what lsmck_sstable_get_batch's index pass proves, kept
+// between calls, and the tables' fences (lsmck_tableset.h).  Opened with
+// LSMCK_DEVICE it borrows the caller's arenas, else it owns device copies.
+struct lsmck_tableset {
+  lsmck_ctx* ctx = nullptr;
+  const uint8_t *data = nullptr, *index = nullptr;  // on the device: the caller's, or d_data / d_index
+  size_t data_bytes = 0, index_bytes = 0, ntab = 0;
+  uint64_t nslots = 0, nitems = 0;
+  long fenced_low = 0, fenced_high = 0;
+  DevBuf<uint8_t> d_data, d_index;
+  DevBuf<lsmck_sstable_span> spans;
+  DevBuf<uint64_t> itemfirst, ioff, ipos;
+  DevBuf<lsmck::mrg::OKey> iok;
+  DevBuf<uint32_t> state, fail;
+  DevBuf<lsmck::ts::Fence> fence;
+  size_t resident_bytes() const {
+    return d_data.cap() + d_index.cap() + spans.cap() * sizeof(lsmck_sstable_span) +
+           (itemfirst.cap() + ioff.cap() + ipos.cap()) * 8 + iok.cap() * sizeof(lsmck::mrg::OKey) +
+           (state.cap() + fail.cap()) * 4 + fence.cap() * sizeof(lsmck::ts::Fence);
+  }
 };
 
 namespace {
@@ -1129,6 +1159,26 @@ int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value) {
     *value = ctx->dbg_walked;
   } else if (!strcmp(key, "db_get_run_hits")) {
     *value = ctx->dbg_run_hits;
+  } else if (!strcmp(key, "tableset_open_index_ns")) {  // the last timed lsmck_tableset_open's stages ("sst_encode_time")
+    *value = ctx->ts_open_timer.ns[0];
+  } else if (!strcmp(key, "tableset_open_fence_ns")) {
+    *value = ctx->ts_open_timer.ns[1];
+  } else if (!strcmp(key, "tableset_runs_ns")) {  // the last timed lsmck_tableset_get_batch's stages
+    *value = ctx->ts_timer.ns[0];
+  } else if (!strcmp(key, "tableset_run_probe_ns")) {
+    *value = ctx->ts_timer.ns[2];
+  } else if (!strcmp(key, "tableset_probe_ns")) {
+    *value = ctx->ts_timer.ns[3];
+  } else if (!strcmp(key, "tableset_resolve_ns")) {
+    *value = ctx->ts_timer.ns[4];
+  } else if (!strcmp(key, "tableset_gather_ns")) {
+    *value = ctx->ts_timer.ns[5];
+  } else if (!strcmp(key, "tableset_probed")) {  // ... and its probe's pairs: looked up, walked, dropped by the fences
+    *value = ctx->ts_probed;
+  } else if (!strcmp(key, "tableset_walked")) {
+    *value = ctx->ts_walked;
+  } else if (!strcmp(key, "tableset_fenced")) {
+    *value = ctx->ts_fenced;
   } else if (!strcmp(key, "sst_get_probed")) {  // ... and its probe's pairs
     *value = ctx->get_probed;
   } else if (!strcmp(key, "sst_get_walked")) {
@@ -3072,11 +3122,16 @@ int lsmck_sstable_get_batch(lsmck_ctx* ctx, const uint8_t* data, size_t data_byt
   return 0;
 }
 
-int lsmck_db_get_batch(lsmck_ctx* ctx, const lsmck_get_run* runs, size_t nrun, const uint8_t* data, size_t data_bytes,
-                       const uint8_t* index, size_t index_bytes, const lsmck_sstable_span* spans, size_t ntab,
-                       const uint8_t* qkeys, size_t qkeys_bytes, const lsmck_get_query* q, size_t n,
-                       lsmck_get_result* res, uint8_t* out, size_t out_cap, uint64_t* out_off, uint64_t* out_bytes,
-                       uint64_t* bad_run_entry, uint64_t* bad_table, uint64_t* bad_query, unsigned flags) {
+}  // extern "C"
+
+// lsmck_db_get_batch, and with S lsmck_tableset_get_batch: the tables are then
+// the set's (data .. ntab are its own, on the device whatever `flags` say), the
+// index pass is left out and the table probe goes behind the fences
+static int db_get(lsmck_ctx* ctx, const lsmck_tableset* S, const lsmck_get_run* runs, size_t nrun, const uint8_t* data,
+                  size_t data_bytes, const uint8_t* index, size_t index_bytes, const lsmck_sstable_span* spans,
+                  size_t ntab, const uint8_t* qkeys, size_t qkeys_bytes, const lsmck_get_query* q, size_t n,
+                  lsmck_get_result* res, uint8_t* out, size_t out_cap, uint64_t* out_off, uint64_t* out_bytes,
+                  uint64_t* bad_run_entry, uint64_t* bad_table, uint64_t* bad_query, unsigned flags) {
   if (bad_run_entry) *bad_run_entry = ~0ull;
   if (bad_table) *bad_table = ~0ull;
   if (bad_query) *bad_query = ~0ull;
@@ -3098,6 +3153,7 @@ int lsmck_db_get_batch(lsmck_ctx* ctx, const lsmck_get_run* runs, size_t nrun, c
   if (out_off && !out_bytes) return lsmck_host::set_error(LSMCK_EINVAL, "db get: null out_bytes with out_off");
   if (out_off && out_cap && !out) return lsmck_host::set_error(LSMCK_EINVAL, "db get: null out");
   if (!ctx) return mem_no_ctx("db get");
+  if (S && S->ctx != ctx) return lsmck_host::set_error(LSMCK_EINVAL, "db get: the set was opened with another context");
   int rc;
   std::lock_guard<std::mutex> lk(ctx->mu);
   DevGuard g(ctx->dev);
@@ -3120,16 +3176,19 @@ int lsmck_db_get_batch(lsmck_ctx* ctx, const lsmck_get_run* runs, size_t nrun, c
   uint64_t* hrf = (uint64_t*)(D.h_runs.get() + desc_bytes);
   hrf[0] = 0;
   for (size_t r = 0; r < nrun; ++r) hr[r] = runs[r], hrf[r + 1] = hrf[r] + runs[r].nent;
-  if (!dev) {  // the host form is staged whole
-    if ((rc = G.data.ensure(data_bytes)) || (rc = G.index.ensure(index_bytes)) || (rc = G.spans.ensure(ntab)) ||
+  if (!dev) {  // the host form is staged whole (a set's tables are on the device already)
+    if ((!S && ((rc = G.data.ensure(data_bytes)) || (rc = G.index.ensure(index_bytes)) || (rc = G.spans.ensure(ntab)))) ||
         (rc = G.qkeys.ensure(qkeys_bytes)) || (rc = G.q.ensure(n)))
       return rc;
-    if (data_bytes) HIPCHK(hipMemcpyAsync(G.data, data, data_bytes, hipMemcpyHostToDevice, st));
-    if (index_bytes) HIPCHK(hipMemcpyAsync(G.index, index, index_bytes, hipMemcpyHostToDevice, st));
-    if (ntab) HIPCHK(hipMemcpyAsync(G.spans, spans, ntab * sizeof(lsmck_sstable_span), hipMemcpyHostToDevice, st));
+    if (!S) {
+      if (data_bytes) HIPCHK(hipMemcpyAsync(G.data, data, data_bytes, hipMemcpyHostToDevice, st));
+      if (index_bytes) HIPCHK(hipMemcpyAsync(G.index, index, index_bytes, hipMemcpyHostToDevice, st));
+      if (ntab) HIPCHK(hipMemcpyAsync(G.spans, spans, ntab * sizeof(lsmck_sstable_span), hipMemcpyHostToDevice, st));
+      A.data = G.data, A.index = G.index, A.spans = G.spans;
+    }
     if (qkeys_bytes) HIPCHK(hipMemcpyAsync(G.qkeys, qkeys, qkeys_bytes, hipMemcpyHostToDevice, st));
     if (n) HIPCHK(hipMemcpyAsync(G.q, q, n * sizeof(lsmck_get_query), hipMemcpyHostToDevice, st));
-    A.data = G.data, A.index = G.index, A.spans = G.spans, A.qkeys = G.qkeys, A.q = G.q;
+    A.qkeys = G.qkeys, A.q = G.q;
     // every run's arenas and entries in one block, each piece at a multiple of 256
     auto up = [](size_t x) { return (x + 255u) & ~(size_t)255u; };
     size_t need = 0;
@@ -3161,43 +3220,46 @@ int lsmck_db_get_batch(lsmck_ctx* ctx, const lsmck_get_run* runs, size_t nrun, c
   A.data_bytes = data_bytes, A.index_bytes = index_bytes, A.qkeys_bytes = qkeys_bytes, A.ntab = ntab, A.n = n;
   A.base = (uint32_t)nrun;
   const size_t nb = (size_t)std::max(lsmk_sst_scan_blocks(ntab), lsmk_sst_scan_blocks(n)) + 1;
-  if ((rc = G.itemfirst.ensure(ntab + 1)) || (rc = G.bsum.ensure(nb)) || (rc = G.state.ensure(ntab)) ||
-      (rc = G.fail.ensure(ntab)) || (rc = G.qok.ensure(n)) || (rc = G.win.ensure(n)) || (rc = G.info.ensure(8)) ||
-      (rc = G.h_info.ensure(8, -1)) || (rc = D.rok.ensure((size_t)nent)) || (rc = D.res.ensure(n)) ||
+  if ((!S && ((rc = G.itemfirst.ensure(ntab + 1)) || (rc = G.state.ensure(ntab)) || (rc = G.fail.ensure(ntab)))) ||
+      (rc = G.bsum.ensure(nb)) || (rc = G.qok.ensure(n)) || (rc = G.win.ensure(n)) || (rc = G.info.ensure(9)) ||
+      (rc = G.h_info.ensure(9, -1)) || (rc = D.rok.ensure((size_t)nent)) || (rc = D.res.ensure(n)) ||
       (gather && ((rc = D.len.ensure(n + 1)) || (rc = D.src.ensure(n)))))
     return rc;
   A.itemfirst = G.itemfirst, A.bsum = G.bsum, A.state = G.state, A.fail = G.fail, A.qok = G.qok, A.win = G.win;
   A.info = G.info;
   B.runs = D.runs, B.rf = D.rf, B.nrun = nrun, B.nent = nent, B.rok = D.rok, B.res = D.res;
   B.len = gather ? D.len.get() : nullptr, B.src = gather ? D.src.get() : nullptr;
-  StageTimer& T = ctx->dbg_timer;
+  StageTimer& T = S ? ctx->ts_timer : ctx->dbg_timer;
   T.begin(ctx->opt.sst_encode_time);
   A.count = T.on ? 1u : 0u;
-  // the items' scratch: as lsmck_sstable_get_batch sizes it
-  A.nslots = ntab ? index_bytes / 16 + ntab : 0;
+  // the items' scratch: as lsmck_sstable_get_batch sizes it; a set brings its own, filled when it was opened
+  A.nslots = S ? S->nslots : ntab ? index_bytes / 16 + ntab : 0;
+  if (S) A.itemfirst = S->itemfirst, A.state = S->state, A.fail = S->fail;
   for (int pass = 0;; ++pass) {
-    if ((rc = G.ioff.ensure((size_t)A.nslots)) || (rc = G.ipos.ensure((size_t)A.nslots)) ||
-        (rc = G.iok.ensure((size_t)A.nslots)))
+    if (!S && ((rc = G.ioff.ensure((size_t)A.nslots)) || (rc = G.ipos.ensure((size_t)A.nslots)) ||
+               (rc = G.iok.ensure((size_t)A.nslots))))
       return rc;
     A.ioff = G.ioff, A.ipos = G.ipos, A.iok = G.iok;
+    if (S) A.ioff = S->ioff, A.ipos = S->ipos, A.iok = S->iok;
     HIPCHK(hipMemsetAsync(A.info, 0xFF, 16, st));
     HIPCHK(hipMemsetAsync(A.info + 2, 0, 24, st));
     HIPCHK(hipMemsetAsync(A.info + 5, 0xFF, 8, st));
-    HIPCHK(hipMemsetAsync(A.info + 6, 0, 16, st));
+    HIPCHK(hipMemsetAsync(A.info + 6, 0, 24, st));
     // 1.-5. everything up to the lengths' scan; the error words and the total come back once
     HIPCHK(T.mark(0, st));
     if (nent && (rc = lsmk_dbg_runs(&B, st))) return launch_rc(rc, "db get run pass kernel");
     HIPCHK(T.mark(1, st));
-    if (ntab && (rc = lsmk_get_index(&A, st))) return launch_rc(rc, "db get index kernels");
+    if (!S && ntab && (rc = lsmk_get_index(&A, st))) return launch_rc(rc, "db get index kernels");
     HIPCHK(T.mark(2, st));
     if (n && (rc = lsmk_get_queries(&A, st))) return launch_rc(rc, "db get query kernel");
     if (n && nent && (rc = lsmk_dbg_probe(&B, st))) return launch_rc(rc, "db get run probe kernel");
     HIPCHK(T.mark(3, st));
-    if (n && (rc = lsmk_get_pairs(&A, st))) return launch_rc(rc, "db get table probe kernel");
+    if (n && (rc = S ? lsmk_ts_pairs(&A, S->fence, st) : lsmk_get_pairs(&A, st)))
+      return launch_rc(rc, "db get table probe kernel");
     HIPCHK(T.mark(4, st));
     if (n && (rc = lsmk_dbg_resolve(&B, st))) return launch_rc(rc, "db get resolve / scan kernels");
     HIPCHK(T.mark(5, st));
-    HIPCHK(hipMemcpyAsync(G.h_info, A.info, 64, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(G.h_info, A.info, 72, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (G.h_info[2] <= A.nslots) break;
     if (pass) return lsmck_host::set_error(LSMCK_EINVAL, "db get: the index arena changed during the call");
@@ -3224,7 +3286,8 @@ int lsmck_db_get_batch(lsmck_ctx* ctx, const lsmck_get_run* runs, size_t nrun, c
     *out_bytes = total;
     if (out_cap < total) return lsmck_host::set_error(LSMCK_ENOSPC, "db get: out_cap is smaller than the values");
   }
-  if (T.on) ctx->dbg_probed = (long)G.h_info[3], ctx->dbg_walked = (long)G.h_info[4], ctx->dbg_run_hits = (long)G.h_info[6];
+  if (T.on && S) ctx->ts_probed = (long)G.h_info[3], ctx->ts_walked = (long)G.h_info[4], ctx->ts_fenced = (long)G.h_info[8];
+  if (T.on && !S) ctx->dbg_probed = (long)G.h_info[3], ctx->dbg_walked = (long)G.h_info[4], ctx->dbg_run_hits = (long)G.h_info[6];
   if (n == 0) {  // (no result; the scan of no lengths)
     if (gather && dev) HIPCHK(hipMemsetAsync(out_off, 0, 8, st));
     if (gather && dev) HIPCHK(hipStreamSynchronize(st));
@@ -3249,6 +3312,139 @@ int lsmck_db_get_batch(lsmck_ctx* ctx, const lsmck_get_run* runs, size_t nrun, c
   HIPCHK(T.span(6, 7, 5));
   T.finish();
   return 0;
+}
+
+extern "C" {
+
+int lsmck_db_get_batch(lsmck_ctx* ctx, const lsmck_get_run* runs, size_t nrun, const uint8_t* data, size_t data_bytes,
+                       const uint8_t* index, size_t index_bytes, const lsmck_sstable_span* spans, size_t ntab,
+                       const uint8_t* qkeys, size_t qkeys_bytes, const lsmck_get_query* q, size_t n,
+                       lsmck_get_result* res, uint8_t* out, size_t out_cap, uint64_t* out_off, uint64_t* out_bytes,
+                       uint64_t* bad_run_entry, uint64_t* bad_table, uint64_t* bad_query, unsigned flags) {
+  return db_get(ctx, nullptr, runs, nrun, data, data_bytes, index, index_bytes, spans, ntab, qkeys, qkeys_bytes, q, n, res,
+                out, out_cap, out_off, out_bytes, bad_run_entry, bad_table, bad_query, flags);
+}
+
+int lsmck_tableset_open(lsmck_ctx* ctx, const uint8_t* data, size_t data_bytes, const uint8_t* index,
+                        size_t index_bytes, const lsmck_sstable_span* spans, size_t ntab, lsmck_tableset** set,
+                        uint64_t* bad_table, unsigned flags) {
+  if (set) *set = nullptr;
+  if (bad_table) *bad_table = ~0ull;
+  if (flags & ~(LSMCK_DEVICE | LSMCK_HOST_PINNED)) return lsmck_host::set_error(LSMCK_EINVAL, "tableset open: unknown flag");
+  if (ntab >= (1ull << 32)) return lsmck_host::set_error(LSMCK_EINVAL, "tableset open: more than 2^32-1 tables in one set");
+  if (ntab && !index) return lsmck_host::set_error(LSMCK_EINVAL, "tableset open: null index");
+  if ((ntab && !spans) || (data_bytes && !data)) return lsmck_host::set_error(LSMCK_EINVAL, "tableset open: null spans or data");
+  if (!set) return lsmck_host::set_error(LSMCK_EINVAL, "tableset open: null set");
+  if (!ctx) return mem_no_ctx("tableset open");
+  int rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DevGuard g(ctx->dev);
+  const hipStream_t st = ctx->stream0;
+  ScratchOrder so(ctx, st);
+  if (so.e != hipSuccess) return hip_error(so.e, "hipStreamWaitEvent(scratch)");
+  auto& G = ctx->get;  // (the scan's block sums and the call's words alone: nothing of the set stays in scratch)
+  const bool dev = (flags & LSMCK_DEVICE) != 0;
+  if (!ntab) index_bytes = 0;
+  std::unique_ptr<lsmck_tableset> S(new lsmck_tableset);  // (freed on every error return, this device current)
+  S->ctx = ctx, S->data = data, S->index = index;
+  S->data_bytes = data_bytes, S->index_bytes = index_bytes, S->ntab = ntab;
+  if (!ntab) {  // the empty set: no table answers
+    S->data = S->index = nullptr, S->data_bytes = 0;
+    *set = S.release();
+    return 0;
+  }
+  if (!dev) {  // the set owns device copies, staged once
+    if ((rc = S->d_data.ensure(data_bytes)) || (rc = S->d_index.ensure(index_bytes))) return rc;
+    if (data_bytes) HIPCHK(hipMemcpyAsync(S->d_data, data, data_bytes, hipMemcpyHostToDevice, st));
+    if (index_bytes) HIPCHK(hipMemcpyAsync(S->d_index, index, index_bytes, hipMemcpyHostToDevice, st));
+    S->data = S->d_data, S->index = S->d_index;
+  }
+  if ((rc = S->spans.ensure(ntab)) || (rc = S->itemfirst.ensure(ntab + 1)) || (rc = S->state.ensure(ntab)) ||
+      (rc = S->fail.ensure(ntab)) || (rc = S->fence.ensure(ntab)) ||
+      (rc = G.bsum.ensure((size_t)lsmk_sst_scan_blocks(ntab) + 1)) || (rc = G.info.ensure(9)) ||
+      (rc = G.h_info.ensure(9, -1)))
+    return rc;
+  HIPCHK(hipMemcpyAsync(S->spans, spans, ntab * sizeof(lsmck_sstable_span),
+                        dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  lsmck::GetArgs A{};
+  A.data = S->data, A.index = S->index, A.spans = S->spans;
+  A.data_bytes = data_bytes, A.index_bytes = index_bytes, A.ntab = ntab;
+  A.itemfirst = S->itemfirst, A.bsum = G.bsum, A.state = S->state, A.fail = S->fail, A.info = G.info;
+  StageTimer& T = ctx->ts_open_timer;
+  T.begin(ctx->opt.sst_encode_time);
+  // the items' arrays: as lsmck_sstable_get_batch sizes its scratch
+  A.nslots = index_bytes / 16 + ntab;
+  for (int pass = 0;; ++pass) {
+    if ((rc = S->ioff.ensure((size_t)A.nslots)) || (rc = S->ipos.ensure((size_t)A.nslots)) ||
+        (rc = S->iok.ensure((size_t)A.nslots)))
+      return rc;
+    A.ioff = S->ioff, A.ipos = S->ipos, A.iok = S->iok;
+    HIPCHK(hipMemsetAsync(A.info, 0xFF, 16, st));
+    HIPCHK(hipMemsetAsync(A.info + 2, 0, 24, st));
+    HIPCHK(T.mark(0, st));
+    if ((rc = lsmk_get_index(&A, st))) return launch_rc(rc, "tableset open index kernels");
+    HIPCHK(T.mark(1, st));
+    if ((rc = lsmk_ts_fences(&A, S->fence, (uint32_t)ctx->opt.fence_walk_cap, st)))
+      return launch_rc(rc, "tableset open fence kernel");
+    HIPCHK(T.mark(2, st));
+    HIPCHK(hipMemcpyAsync(G.h_info, A.info, 40, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (G.h_info[2] <= A.nslots) break;
+    if (pass) return lsmck_host::set_error(LSMCK_EINVAL, "tableset open: the index arena changed during the call");
+    A.nslots = G.h_info[2];
+  }
+  if (G.h_info[0] != ~0ull) {
+    if (bad_table) *bad_table = G.h_info[0];
+    return lsmck_host::set_error(LSMCK_EINVAL,
+                                 "tableset open: a table's span lies outside its arena, its data file is above 2^32-1 "
+                                 "bytes, or its index is not a map image with strictly increasing keys");
+  }
+  S->nslots = A.nslots, S->nitems = G.h_info[2];
+  S->fenced_low = (long)G.h_info[3], S->fenced_high = (long)G.h_info[4];
+  HIPCHK(T.span(0, 1, 0));
+  HIPCHK(T.span(1, 2, 1));
+  T.finish();
+  *set = S.release();
+  return 0;
+}
+
+int lsmck_tableset_get_batch(lsmck_ctx* ctx, const lsmck_tableset* set, const lsmck_get_run* runs, size_t nrun,
+                             const uint8_t* qkeys, size_t qkeys_bytes, const lsmck_get_query* q, size_t n,
+                             lsmck_get_result* res, uint8_t* out, size_t out_cap, uint64_t* out_off,
+                             uint64_t* out_bytes, uint64_t* bad_run_entry, uint64_t* bad_query, unsigned flags) {
+  if (!set) {
+    if (bad_run_entry) *bad_run_entry = ~0ull;
+    if (bad_query) *bad_query = ~0ull;
+    if (out_bytes) *out_bytes = 0;
+    return lsmck_host::set_error(LSMCK_EINVAL, "tableset get: null set");
+  }
+  return db_get(ctx, set, runs, nrun, set->data, set->data_bytes, set->index, set->index_bytes, set->spans, set->ntab,
+                qkeys, qkeys_bytes, q, n, res, out, out_cap, out_off, out_bytes, bad_run_entry, nullptr, bad_query, flags);
+}
+
+int lsmck_tableset_stat(const lsmck_tableset* set, const char* key, long* value) {
+  if (!set || !key || !value) return lsmck_host::set_error(LSMCK_EINVAL, "tableset stat: null set, key or value");
+  if (!strcmp(key, "tables")) {
+    *value = (long)set->ntab;
+  } else if (!strcmp(key, "items")) {
+    *value = (long)set->nitems;
+  } else if (!strcmp(key, "fenced_low")) {
+    *value = set->fenced_low;
+  } else if (!strcmp(key, "fenced_high")) {
+    *value = set->fenced_high;
+  } else if (!strcmp(key, "resident_bytes")) {
+    *value = (long)set->resident_bytes();
+  } else {
+    return lsmck_host::set_error(LSMCK_EINVAL, "tableset stat: unknown stat");
+  }
+  return 0;
+}
+
+void lsmck_tableset_close(lsmck_tableset* set) {
+  if (!set) return;
+  std::lock_guard<std::mutex> lk(set->ctx->mu);  // (no call of the context is using the set)
+  DevGuard g(set->ctx->dev);
+  delete set;
 }
 
 }  // extern "C"

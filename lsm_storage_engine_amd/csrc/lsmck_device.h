@@ -171,7 +171,9 @@ struct GetArgs {
 // then the lengths' exclusive scan; n + 1; null without a gather) and src (its
 // value's address).  g.info[5] = the first run entry refused (atomic min, set
 // to ~0 by the caller), [6] the queries a run answered (set to 0), [7] the
-// gathered bytes.
+// gathered bytes, [8] the pairs an opened set's fences dropped (set to 0;
+// lsmck_tableset.hip, whose table arrays lie in the set and not in scratch).
+namespace ts { struct Fence; }
 struct DbArgs {
   GetArgs g;
   const lsmck_get_run* runs;
@@ -197,6 +199,9 @@ int lsmk_get_probe(const lsmck::GetArgs* a, hipStream_t st);  // the queries' ch
 int lsmk_get_queries(const lsmck::GetArgs* a, hipStream_t st);  // the queries' check, order keys, win = none (n > 0)
 int lsmk_get_pairs(const lsmck::GetArgs* a, hipStream_t st);    // every (query, table) pair: a winner is a->base + t
 int lsmk_get_resolve(const lsmck::GetArgs* a, lsmck_get_result* res, hipStream_t st);
+// opened table set (lsmck_tableset.hip)
+int lsmk_ts_fences(const lsmck::GetArgs* a, lsmck::ts::Fence* fence, uint32_t cap, hipStream_t st);  // behind lsmk_get_index
+int lsmk_ts_pairs(const lsmck::GetArgs* a, const lsmck::ts::Fence* fence, hipStream_t st);  // lsmk_get_pairs behind the fences
 // batch SSTable decode and merge (lsmck_sstmerge.hip); ntab > 0 and n > 0
 int lsmk_dec_index(const lsmck::DecArgs* a, hipStream_t st);     // spans, index parse, segment starts
 int lsmk_dec_segments(const lsmck::DecArgs* a, hipStream_t st);  // the segments' check

@@ -39,6 +39,8 @@ struct Options {
   long wal_encode_time = 0, sst_encode_time = 0, mem_build_time = 0;
   // the batch write plan: a candidate start's walk steps at most, the starts a workgroup links in LDS
   long cut_walk_cap = 4096, cut_block = 8192;
+  // the opened table set: the records a fence's walk visits at most (lsmck_tableset.h; read when a set is opened)
+  long fence_walk_cap = 256;
 };
 
 // `variant` bits
@@ -139,6 +141,10 @@ constexpr OptionRow kPlanOptions[] = {
     LSMCK_OPT(cut_walk_cap, 1, 1l << 30),
     LSMCK_OPT(cut_block, 64, 8192),
 };
+// the opened table set's (lsmck_tableset_open), looked up behind kPlanOptions
+constexpr OptionRow kSetOptions[] = {
+    LSMCK_OPT(fence_walk_cap, 1, 1l << 20),
+};
 #undef LSMCK_OPT
 
 // Looks `key` up, checks `value` against its row and stores it.  Returns 0, or
@@ -147,8 +153,11 @@ inline int option_set(Options& o, const char* key, long value, const OptionEnv& 
   if (!key) return *why = "null key", LSMCK_EINVAL;
   constexpr size_t kRows = sizeof kOptions / sizeof kOptions[0];
   constexpr size_t kPlanRows = sizeof kPlanOptions / sizeof kPlanOptions[0];
-  for (size_t i = 0; i < kRows + kPlanRows; ++i) {
-    const OptionRow& r = i < kRows ? kOptions[i] : kPlanOptions[i - kRows];
+  constexpr size_t kSetRows = sizeof kSetOptions / sizeof kSetOptions[0];
+  for (size_t i = 0; i < kRows + kPlanRows + kSetRows; ++i) {
+    const OptionRow& r = i < kRows               ? kOptions[i]
+                         : i < kRows + kPlanRows ? kPlanOptions[i - kRows]
+                                                 : kSetOptions[i - kRows - kPlanRows];
     if (strcmp(key, r.name)) continue;
     if (r.accepts) {
       if (!r.accepts(r, value, env, why)) return LSMCK_EINVAL;

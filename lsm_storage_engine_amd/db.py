@@ -97,6 +97,52 @@ def get_many(memtables, levels, keys, ctx=None, internal=False):
     return out
 
 
+class Reader:
+    """A reader that loads its tables once (SsTable::load,
+    tokio/sstable.rs:32-55) and then serves gets until a compaction replaces
+    them: ``levels``' files are read once and opened as one
+    lsmck_tableset_open set on ``ctx`` -- the index pass and the tables' key
+    fences stay on the device -- and ``get_many`` is one
+    lsmck_tableset_get_batch call.  ``close()`` frees the set."""
+
+    def __init__(self, levels, ctx):
+        order = [m for level in levels for m in reversed(level)]
+        datas = [open(m.data_path(), "rb").read() for m in order]
+        idxs = [open(m.index_path(), "rb").read() for m in order]
+        spans = np.zeros(len(order), dtype=_lib.SSTABLE_SPAN_DTYPE)
+        spans["data_len"], spans["index_len"] = [len(d) for d in datas], [len(x) for x in idxs]
+        spans["data_off"] = np.cumsum(spans["data_len"]) - spans["data_len"]
+        spans["index_off"] = np.cumsum(spans["index_len"]) - spans["index_len"]
+        self.set = ctx.tableset_open(np.frombuffer(b"".join(datas), np.uint8), np.frombuffer(b"".join(idxs), np.uint8),
+                                     spans)
+
+    def get_many(self, memtables, keys, internal=False):
+        """``get_many(memtables, levels, keys, ctx, internal)`` over the opened tables: the same answers."""
+        keys = [bytes(k) for k in keys]
+        q = np.zeros(len(keys), dtype=_lib.GET_QUERY_DTYPE)
+        klen = np.fromiter((len(k) for k in keys), dtype=np.uint64, count=len(keys))
+        q["klen"], q["key_off"] = klen, np.cumsum(klen) - klen
+        res, off, vals = self.set.get_batch([run_arrays(m) for m in memtables], np.frombuffer(b"".join(keys), np.uint8), q)
+        arena, off, out = vals.tobytes(), off.tolist(), []
+        for i, (table, val_off) in enumerate(zip(res["table"].tolist(), res["val_off"].tolist())):
+            if table == _lib.GET_NONE:
+                out.append(None)
+            elif val_off & _lib.GET_TOMBSTONE:
+                out.append(TOMBSTONE_HIT if internal else None)
+            else:
+                out.append(arena[off[i]:off[i + 1]])
+        return out
+
+    def close(self):
+        self.set.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 def _write_loop(base_path, commands, limit, stamps):
     """LsmStorage::insert / delete, command by command (lsm_storage.rs:59-78, 133-139)."""
     from . import wal
@@ -205,4 +251,4 @@ def write_many(base_path, commands, limit, ctx=None, timestamps_ms=None):
             b.free()
 
 
-__all__ = ["get_many", "run_arrays", "write_many", "TOMBSTONE_HIT", "DELETED"]
+__all__ = ["get_many", "Reader", "run_arrays", "write_many", "TOMBSTONE_HIT", "DELETED"]

@@ -193,6 +193,102 @@ class DbGetError(_lib.LsmckError):
                              f"needed={needed})")
 
 
+class TableSet:
+    """An opened table set (lsmck_tableset_open): ``Context.tableset_open``
+    makes one.  It holds its context, so the context outlives it; ``close()``
+    (or leaving the ``with`` block) frees the device buffers it owns."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.handle = ctx, handle
+
+    def close(self):
+        if self.handle and self.ctx.handle:
+            self.ctx.lib.lsmck_tableset_close(self.handle)
+        self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def stat(self, key):
+        """lsmck_tableset_stat: "tables", "items", "fenced_low", "fenced_high", "resident_bytes"."""
+        v = C.c_long()
+        _lib.check(self.ctx.lib.lsmck_tableset_stat(self.handle, key.encode(), C.byref(v)), f"tableset_stat({key})")
+        return v.value
+
+    def _get(self, ctx, runs, qkeys, qb, q, n, res, out, out_cap, out_off, flags):
+        none = 2 ** 64 - 1
+        runs = np.ascontiguousarray(runs, dtype=_lib.GET_RUN_DTYPE)
+        br, bq, nbytes = C.c_uint64(none), C.c_uint64(none), C.c_uint64(0)
+        rc = ctx.lib.lsmck_tableset_get_batch(ctx.handle, self.handle, runs.ctypes.data if len(runs) else None, len(runs),
+                                              qkeys, qb, q, n, res, out, out_cap, out_off, C.byref(nbytes), C.byref(br),
+                                              C.byref(bq), flags)
+        if rc == _lib.EINVAL:
+            raise DbGetError(rc, "tableset_get_batch", bad_run_entry=None if br.value == none else br.value,
+                             bad_query=None if bq.value == none else bq.value)
+        if rc == _lib.ENOSPC:
+            raise DbGetError(rc, "tableset_get_batch", needed=nbytes.value)
+        _lib.check(rc, "tableset_get_batch")
+        return nbytes.value
+
+    def get_batch(self, runs, qkeys, queries, values=True, pinned=False, out_guess=1 << 20):
+        """lsmck_tableset_get_batch, host form: ``Context.db_get_batch`` with
+        the set in place of (data, index, spans); the same three results,
+        ``val_off`` of a table's answer into the data arena the set was opened
+        over.  Raises DbGetError."""
+        keep, desc = [], np.zeros(len(runs), dtype=_lib.GET_RUN_DTYPE)
+        for r, (keys, vals, ents) in enumerate(runs):
+            keys = np.ascontiguousarray(keys, dtype=np.uint8)
+            vals = keys if vals is keys else np.ascontiguousarray(vals, dtype=np.uint8)
+            ents = np.ascontiguousarray(ents, dtype=_lib.WAL_CMD_DTYPE)
+            keep.append((keys, vals, ents))
+            desc[r] = (keys.ctypes.data if keys.nbytes else 0, keys.nbytes, vals.ctypes.data if vals.nbytes else 0,
+                       vals.nbytes, ents.ctypes.data if len(ents) else 0, len(ents))
+        qkeys = np.ascontiguousarray(qkeys, dtype=np.uint8)
+        queries = np.ascontiguousarray(queries, dtype=_lib.GET_QUERY_DTYPE)
+        n = len(queries)
+        res = np.empty(n, dtype=_lib.GET_RESULT_DTYPE)
+        flags = _lib.HOST_PINNED if pinned else _lib.HOST
+        args = (self.ctx, desc, _p(qkeys), qkeys.nbytes, _p(queries), n, _p(res))
+        if not values:
+            self._get(*args, None, 0, None, flags)
+            return res, None, None
+        off = np.empty(n + 1, dtype=np.uint64)
+        out = np.empty(max(out_guess, 1), dtype=np.uint8)  # (a guess: the call names the size when it is too small)
+        try:
+            total = self._get(*args, _p(out), out.nbytes, off.ctypes.data, flags)
+        except DbGetError as e:
+            if e.needed is None:
+                raise
+            out = np.empty(e.needed, dtype=np.uint8)
+            total = self._get(*args, _p(out), out.nbytes, off.ctypes.data, flags)
+        return res, off, out[:total]
+
+    def get_batch_device(self, runs, qkeys_ptr, qkeys_bytes, queries_ptr, n, res_ptr, out_ptr=None, out_cap=0,
+                         out_off_ptr=None, ctx=None):
+        """lsmck_tableset_get_batch on device pointers: ``runs`` and the
+        outputs as in ``Context.db_get_batch_device``.  ``ctx``: the calling
+        context (the set's own; another one is refused).  Returns the
+        gathered bytes; raises DbGetError; nothing was written then."""
+        if not isinstance(runs, np.ndarray):
+            desc = np.zeros(len(runs), dtype=_lib.GET_RUN_DTYPE)
+            for r, run in enumerate(runs):
+                if hasattr(run, "image_bytes"):
+                    run = (run.image.ptr, run.image_bytes, run.image.ptr, run.image_bytes, run.ents.ptr, run.nent)
+                desc[r] = tuple(0 if x is None else int(x) for x in run)
+            runs = desc
+        return self._get(self.ctx if ctx is None else ctx, runs, qkeys_ptr, qkeys_bytes, queries_ptr, n, res_ptr, out_ptr,
+                         out_cap, out_off_ptr, _lib.DEVICE)
+
+
 class Context:
     def __init__(self, device=0):
         lib = _lib.load()
@@ -720,6 +816,30 @@ class Context:
             runs = desc
         return self._db_get(runs, data_ptr, data_bytes, index_ptr, index_bytes, spans_ptr, ntab, qkeys_ptr, qkeys_bytes,
                             queries_ptr, n, res_ptr, out_ptr, out_cap, out_off_ptr, _lib.DEVICE)
+
+    def tableset_open(self, data, index, spans, ntab=None, data_bytes=None, index_bytes=None, pinned=False):
+        """lsmck_tableset_open: the tables of ``sstable_get_batch`` opened once
+        -- the index pass and the key fences stay on the device.  Host form:
+        ``data`` and ``index`` uint8 arrays, ``spans`` SSTABLE_SPAN_DTYPE; the
+        set owns device copies.  Device form (``ntab`` given): three device
+        pointers with ``data_bytes`` and ``index_bytes``; the set borrows data
+        and index, which stay alive and unchanged until it is closed.  Returns
+        a ``TableSet``; raises SstGetError (``bad_table``)."""
+        if ntab is None:
+            data = np.ascontiguousarray(data, dtype=np.uint8)
+            index = np.ascontiguousarray(index, dtype=np.uint8)
+            spans = np.ascontiguousarray(spans, dtype=_lib.SSTABLE_SPAN_DTYPE)
+            args = (_p(data), data.nbytes, _p(index), index.nbytes, _p(spans), len(spans))
+            flags = _lib.HOST_PINNED if pinned else _lib.HOST
+        else:
+            args, flags = (data, data_bytes, index, index_bytes, spans, ntab), _lib.DEVICE
+        none = 2 ** 64 - 1
+        handle, bt = C.c_void_p(), C.c_uint64(none)
+        rc = self.lib.lsmck_tableset_open(self.handle, *args, C.byref(handle), C.byref(bt), flags)
+        if rc == _lib.EINVAL:
+            raise SstGetError(rc, "tableset_open", bad_table=None if bt.value == none else bt.value)
+        _lib.check(rc, "tableset_open")
+        return TableSet(self, handle.value)
 
     def _write_plan(self, keys, kb, vals, vb, cmds, n, limit, tomb_off, ents, ent_cap, src, segs, seg_cap, flags):
         none = 2 ** 64 - 1
