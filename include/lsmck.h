@@ -302,6 +302,11 @@ int lsmck_device_count(void);
  *                 at most (default 256, 1..2^20; INDEX_STEP is 100 and an
  *                 interval with one item missing 200).  Read when a set is
  *                 opened; a longer head or tail leaves that fence invalid.
+ *   "bloom_bits"  lsmck_tableset_open: the bits per key of a resident bloom
+ *                 filter per table (default 0: no filters; 4..64).  Read when
+ *                 a set is opened, as "fence_walk_cap" is, whose cap the
+ *                 filters' walks share; lsmck_ctx_get_stat("bloom_bits") is
+ *                 the value in effect.  No result of any call depends on it.
  * Returns 0, or LSMCK_EINVAL for an unknown key / value. */
 int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value);
 
@@ -994,6 +999,18 @@ int lsmck_db_get_batch(lsmck_ctx* ctx, const lsmck_get_run* runs, size_t nrun, c
  * argument), for positions that are any u64, records that hold any key, and
  * tails that are unsorted or cut: a fenced (query, table) pair costs two key
  * compares and no lookup, and no result differs.
+ * BLOOM FILTERS ("bloom_bits" > 0): the role of SsTable::get's first line
+ * (src/sync/sstable.rs:98), built from the tables' own bytes at open and kept
+ * on the device; not the reference's bloom file.  A table's key set is every
+ * item key of at most 2^32-1 bytes and the key of every record its m + 1
+ * interval walks visit (scan_range(0, pos_0), scan_range(pos_j, pos_{j+1}),
+ * scan_range(pos_{m-1}, L); m == 0: scan_range(0, L)); the table has a filter
+ * when each walk ends within "fence_walk_cap" records.  SsTable::get answers
+ * Some only for an item key or for a record one of those walks visits, so a
+ * pair the filter drops is None whatever the table's bytes are
+ * (lsmck_bloom.h has the argument and the split-block layout); a table
+ * without a filter is simply looked up.  A get hashes every query once and
+ * tests a pair that passed the fences with one 32-byte load.
  * open (tokio/sstable.rs:32-55).  The rules, the refusals, the first
  * bad_table and the cases checked before any GPU work are
  * lsmck_sstable_get_batch's, word for word.  flags: LSMCK_DEVICE -- data,
@@ -1015,20 +1032,27 @@ int lsmck_db_get_batch(lsmck_ctx* ctx, const lsmck_get_run* runs, size_t nrun, c
  * kernels of lsmck_db_get_batch without the index pass, and a table probe
  * that tests the fences before it looks anything up.
  * stat.  "tables", "items" (index items of all tables), "fenced_low" and
- * "fenced_high" (the tables with each fence), "resident_bytes" (device bytes
- * the set owns).  LSMCK_EINVAL for an unknown key or a NULL argument.
+ * "fenced_high" (the tables with each fence), "bloom_tables" (the tables with
+ * a filter), "bloom_keys" (their keys, duplicates counted), "bloom_bytes" (the
+ * filters' blocks and the 16-byte descriptor per table; 0 for a set opened
+ * without filters), "resident_bytes" (device bytes the set owns, the filters'
+ * among them).  LSMCK_EINVAL for an unknown key or a NULL argument.
  * close.  Frees the set; NULL is a no-op.  Sets are closed before their
  * context is destroyed.
- * With "sst_encode_time" 1, lsmck_ctx_get_stat has "tableset_open_index_ns" and
- * "tableset_open_fence_ns" for the last open, and for the last get
+ * With "sst_encode_time" 1, lsmck_ctx_get_stat has "tableset_open_index_ns",
+ * "tableset_open_fence_ns" and "tableset_open_bloom_ns" (the filters' count,
+ * sizes and fill; 0 without them) for the last open, and for the last get
  * "tableset_runs_ns", "tableset_run_probe_ns", "tableset_probe_ns",
  * "tableset_resolve_ns", "tableset_gather_ns", and "tableset_probed" /
  * "tableset_walked" / "tableset_fenced": the (query, table) pairs looked up,
  * those whose interval was walked, and those the fences dropped (counted
- * before the check for a lower source's answer, so a fixed number per input).
+ * before the check for a lower source's answer, so a fixed number per input);
+ * and "tableset_bloomed": the pairs that passed the fences and that the
+ * filters dropped, counted the same way.
  * Not covered: an opened run form, sorting queries by interval, a
  * host-resident opened table for the scalar lsmck_sstable_get, fences for a
- * table without index items, the bloom file. */
+ * table without index items, the reference's bloom file (bincode of a crate's
+ * filter with hashers keyed from entropy), filters for runs. */
 typedef struct lsmck_tableset lsmck_tableset;
 int lsmck_tableset_open(lsmck_ctx* ctx, const uint8_t* data, size_t data_bytes, const uint8_t* index,
                         size_t index_bytes, const lsmck_sstable_span* spans, size_t ntab, lsmck_tableset** set,

@@ -45,6 +45,7 @@
 #include "lsmck_pool.h"
 #include "lsmck_segwalk.h"
 #include "lsmck_sstmerge.h"
+#include "lsmck_bloom.h"
 #include "lsmck_tableset.h"
 
 using lsmck::CrcParams;
@@ -500,6 +501,7 @@ struct lsmck_ctx {
     DevBuf<lsmck_get_result> res;
     DevBuf<uint8_t> stage, out;
     PinBuf<uint8_t> h_runs;
+    DevBuf<uint64_t> qh;  // lsmck_tableset_get_batch on a set with filters: the queries' hashes (lsmck_bloom.h)
   } dbg;
   StageTimer dbg_timer;  // "sst_encode_time" (this call too): run pass, index pass, run probe, table probe, resolve / scan, gather
   long dbg_probed = 0;   // the last timed call's (query, table) pairs looked up
@@ -507,11 +509,12 @@ struct lsmck_ctx {
   long dbg_run_hits = 0;  // ... and its queries a run answered
   // opened table sets (lsmck_tableset below): the tables' arrays live in the
   // set; a get's per-query scratch is `get` and `dbg` above
-  StageTimer ts_open_timer;  // "sst_encode_time" (lsmck_tableset_open): index pass, fences
+  StageTimer ts_open_timer;  // "sst_encode_time" (lsmck_tableset_open): index pass, fences, filters ("bloom_bits" > 0)
   StageTimer ts_timer;       // ... (lsmck_tableset_get_batch): dbg_timer's stages, the index pass's always 0
   long ts_probed = 0;        // the last timed get's (query, table) pairs looked up
   long ts_walked = 0;        // ... whose interval was walked
   long ts_fenced = 0;        // ... and those the fences dropped
+  long ts_bloomed = 0;       // ... and those that passed the fences and the filters dropped
   bool wal_recs_direct = false;  // this replay's records go by DMA into the caller's pinned array (under wal_mu)
   bool wal_compact = false;      // this replay's records are lsmck_wal_rec16 (under wal_mu)
   // LSMCK_RECS_DEVICE (under wal_mu): the caller's device array and its capacity
@@ -573,24 +576,29 @@ struct lsmck_ctx {
 };
 
 // An opened table set: what lsmck_sstable_get_batch's index pass proves, kept
-// between calls, and the tables' fences (lsmck_tableset.h).  Opened with
-// LSMCK_DEVICE it borrows the caller's arenas, else it owns device copies.
+// between calls, the tables' fences (lsmck_tableset.h) and, opened with
+// "bloom_bits" > 0, their filters (lsmck_bloom.h).  Opened with LSMCK_DEVICE
+// it borrows the caller's arenas, else it owns device copies.
 struct lsmck_tableset {
   lsmck_ctx* ctx = nullptr;
   const uint8_t *data = nullptr, *index = nullptr;  // on the device: the caller's, or d_data / d_index
   size_t data_bytes = 0, index_bytes = 0, ntab = 0;
   uint64_t nslots = 0, nitems = 0;
   long fenced_low = 0, fenced_high = 0;
+  long bloom_tables = 0, bloom_keys = 0;  // the tables with a filter, their keys
   DevBuf<uint8_t> d_data, d_index;
   DevBuf<lsmck_sstable_span> spans;
   DevBuf<uint64_t> itemfirst, ioff, ipos;
   DevBuf<lsmck::mrg::OKey> iok;
   DevBuf<uint32_t> state, fail;
   DevBuf<lsmck::ts::Fence> fence;
+  DevBuf<lsmck::blm::Desc> bdesc;  // per table ("bloom_bits" > 0)
+  DevBuf<uint32_t> bfilt;          // the filters' blocks
+  size_t bloom_bytes() const { return bdesc.cap() * sizeof(lsmck::blm::Desc) + bfilt.cap() * 4; }
   size_t resident_bytes() const {
     return d_data.cap() + d_index.cap() + spans.cap() * sizeof(lsmck_sstable_span) +
            (itemfirst.cap() + ioff.cap() + ipos.cap()) * 8 + iok.cap() * sizeof(lsmck::mrg::OKey) +
-           (state.cap() + fail.cap()) * 4 + fence.cap() * sizeof(lsmck::ts::Fence);
+           (state.cap() + fail.cap()) * 4 + fence.cap() * sizeof(lsmck::ts::Fence) + bloom_bytes();
   }
 };
 
@@ -1163,6 +1171,10 @@ int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value) {
     *value = ctx->ts_open_timer.ns[0];
   } else if (!strcmp(key, "tableset_open_fence_ns")) {
     *value = ctx->ts_open_timer.ns[1];
+  } else if (!strcmp(key, "bloom_bits")) {  // the option's value (a caller that sets it around an open restores it)
+    *value = ctx->opt.bloom_bits;
+  } else if (!strcmp(key, "tableset_open_bloom_ns")) {
+    *value = ctx->ts_open_timer.ns[2];
   } else if (!strcmp(key, "tableset_runs_ns")) {  // the last timed lsmck_tableset_get_batch's stages
     *value = ctx->ts_timer.ns[0];
   } else if (!strcmp(key, "tableset_run_probe_ns")) {
@@ -1179,6 +1191,8 @@ int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value) {
     *value = ctx->ts_walked;
   } else if (!strcmp(key, "tableset_fenced")) {
     *value = ctx->ts_fenced;
+  } else if (!strcmp(key, "tableset_bloomed")) {  // ... and, behind the fences, by the filters
+    *value = ctx->ts_bloomed;
   } else if (!strcmp(key, "sst_get_probed")) {  // ... and its probe's pairs
     *value = ctx->get_probed;
   } else if (!strcmp(key, "sst_get_walked")) {
@@ -3221,10 +3235,12 @@ static int db_get(lsmck_ctx* ctx, const lsmck_tableset* S, const lsmck_get_run* 
   A.base = (uint32_t)nrun;
   const size_t nb = (size_t)std::max(lsmk_sst_scan_blocks(ntab), lsmk_sst_scan_blocks(n)) + 1;
   if ((!S && ((rc = G.itemfirst.ensure(ntab + 1)) || (rc = G.state.ensure(ntab)) || (rc = G.fail.ensure(ntab)))) ||
-      (rc = G.bsum.ensure(nb)) || (rc = G.qok.ensure(n)) || (rc = G.win.ensure(n)) || (rc = G.info.ensure(9)) ||
-      (rc = G.h_info.ensure(9, -1)) || (rc = D.rok.ensure((size_t)nent)) || (rc = D.res.ensure(n)) ||
+      (rc = G.bsum.ensure(nb)) || (rc = G.qok.ensure(n)) || (rc = G.win.ensure(n)) || (rc = G.info.ensure(10)) ||
+      (rc = G.h_info.ensure(10, -1)) || (rc = D.rok.ensure((size_t)nent)) || (rc = D.res.ensure(n)) ||
       (gather && ((rc = D.len.ensure(n + 1)) || (rc = D.src.ensure(n)))))
     return rc;
+  const bool bloom = S && S->bloom_tables > 0;  // the set has a filter: the queries are hashed once, the probe tests them
+  if (bloom && (rc = D.qh.ensure(n))) return rc;
   A.itemfirst = G.itemfirst, A.bsum = G.bsum, A.state = G.state, A.fail = G.fail, A.qok = G.qok, A.win = G.win;
   A.info = G.info;
   B.runs = D.runs, B.rf = D.rf, B.nrun = nrun, B.nent = nent, B.rok = D.rok, B.res = D.res;
@@ -3244,7 +3260,7 @@ static int db_get(lsmck_ctx* ctx, const lsmck_tableset* S, const lsmck_get_run* 
     HIPCHK(hipMemsetAsync(A.info, 0xFF, 16, st));
     HIPCHK(hipMemsetAsync(A.info + 2, 0, 24, st));
     HIPCHK(hipMemsetAsync(A.info + 5, 0xFF, 8, st));
-    HIPCHK(hipMemsetAsync(A.info + 6, 0, 24, st));
+    HIPCHK(hipMemsetAsync(A.info + 6, 0, 32, st));
     // 1.-5. everything up to the lengths' scan; the error words and the total come back once
     HIPCHK(T.mark(0, st));
     if (nent && (rc = lsmk_dbg_runs(&B, st))) return launch_rc(rc, "db get run pass kernel");
@@ -3254,12 +3270,14 @@ static int db_get(lsmck_ctx* ctx, const lsmck_tableset* S, const lsmck_get_run* 
     if (n && (rc = lsmk_get_queries(&A, st))) return launch_rc(rc, "db get query kernel");
     if (n && nent && (rc = lsmk_dbg_probe(&B, st))) return launch_rc(rc, "db get run probe kernel");
     HIPCHK(T.mark(3, st));
-    if (n && (rc = S ? lsmk_ts_pairs(&A, S->fence, st) : lsmk_get_pairs(&A, st)))
+    if (n && bloom && ntab && (rc = lsmk_ts_hash(&A, D.qh, st))) return launch_rc(rc, "tableset get hash kernel");
+    if (n && (rc = S ? lsmk_ts_pairs(&A, S->fence, bloom ? S->bdesc.get() : nullptr, S->bfilt, D.qh, st)
+                     : lsmk_get_pairs(&A, st)))
       return launch_rc(rc, "db get table probe kernel");
     HIPCHK(T.mark(4, st));
     if (n && (rc = lsmk_dbg_resolve(&B, st))) return launch_rc(rc, "db get resolve / scan kernels");
     HIPCHK(T.mark(5, st));
-    HIPCHK(hipMemcpyAsync(G.h_info, A.info, 72, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(G.h_info, A.info, 80, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (G.h_info[2] <= A.nslots) break;
     if (pass) return lsmck_host::set_error(LSMCK_EINVAL, "db get: the index arena changed during the call");
@@ -3287,6 +3305,7 @@ static int db_get(lsmck_ctx* ctx, const lsmck_tableset* S, const lsmck_get_run* 
     if (out_cap < total) return lsmck_host::set_error(LSMCK_ENOSPC, "db get: out_cap is smaller than the values");
   }
   if (T.on && S) ctx->ts_probed = (long)G.h_info[3], ctx->ts_walked = (long)G.h_info[4], ctx->ts_fenced = (long)G.h_info[8];
+  if (T.on && S) ctx->ts_bloomed = (long)G.h_info[9];
   if (T.on && !S) ctx->dbg_probed = (long)G.h_info[3], ctx->dbg_walked = (long)G.h_info[4], ctx->dbg_run_hits = (long)G.h_info[6];
   if (n == 0) {  // (no result; the scan of no lengths)
     if (gather && dev) HIPCHK(hipMemsetAsync(out_off, 0, 8, st));
@@ -3403,6 +3422,34 @@ int lsmck_tableset_open(lsmck_ctx* ctx, const uint8_t* data, size_t data_bytes, 
   S->fenced_low = (long)G.h_info[3], S->fenced_high = (long)G.h_info[4];
   HIPCHK(T.span(0, 1, 0));
   HIPCHK(T.span(1, 2, 1));
+  if (const uint32_t bits = (uint32_t)ctx->opt.bloom_bits) {
+    // the filters (lsmck_bloom.h): a lane per (table, interval) counts, the sizes come back, the same lanes fill
+    const uint32_t cap = (uint32_t)ctx->opt.fence_walk_cap;
+    const uint64_t lanes = S->nitems + ntab;
+    DevBuf<unsigned long long> nkeys;  // (the open's alone: freed on return)
+    DevBuf<uint32_t> over;
+    if ((rc = nkeys.ensure(ntab)) || (rc = over.ensure(ntab)) || (rc = S->bdesc.ensure(ntab))) return rc;
+    HIPCHK(hipMemsetAsync(nkeys, 0, ntab * 8, st));
+    HIPCHK(hipMemsetAsync(over, 0, ntab * 4, st));
+    HIPCHK(hipMemsetAsync(A.info + 5, 0, 24, st));
+    HIPCHK(T.mark(3, st));
+    if ((rc = lsmk_ts_bloom_count(&A, lanes, cap, nkeys, over, st)) ||
+        (rc = lsmk_ts_bloom_size(ntab, bits, nkeys, over, S->bdesc, A.info, st)))
+      return launch_rc(rc, "tableset open filter count kernels");
+    HIPCHK(hipMemcpyAsync(G.h_info + 5, A.info + 5, 24, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    S->bloom_tables = (long)G.h_info[5], S->bloom_keys = (long)G.h_info[6];
+    const uint64_t words = G.h_info[7] * lsmck::blm::kWords;
+    if (words) {
+      if ((rc = S->bfilt.ensure((size_t)words))) return rc;
+      HIPCHK(hipMemsetAsync(S->bfilt, 0, (size_t)words * 4, st));
+      if ((rc = lsmk_ts_bloom_fill(&A, lanes, cap, S->bdesc, S->bfilt, st)))
+        return launch_rc(rc, "tableset open filter fill kernel");
+    }
+    HIPCHK(T.mark(4, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(T.span(3, 4, 2));
+  }
   T.finish();
   *set = S.release();
   return 0;
@@ -3432,6 +3479,12 @@ int lsmck_tableset_stat(const lsmck_tableset* set, const char* key, long* value)
     *value = set->fenced_low;
   } else if (!strcmp(key, "fenced_high")) {
     *value = set->fenced_high;
+  } else if (!strcmp(key, "bloom_tables")) {
+    *value = set->bloom_tables;
+  } else if (!strcmp(key, "bloom_keys")) {
+    *value = set->bloom_keys;
+  } else if (!strcmp(key, "bloom_bytes")) {
+    *value = (long)set->bloom_bytes();
   } else if (!strcmp(key, "resident_bytes")) {
     *value = (long)set->resident_bytes();
   } else {

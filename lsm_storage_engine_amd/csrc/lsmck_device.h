@@ -164,7 +164,7 @@ struct GetArgs {
   uint32_t base;
 };
 // The batch Db::get's (lsmck_dbget.hip dbg_*): the point read's arguments --
-// g.base = nrun, g.info holding 8 words -- and the runs.  runs: the
+// g.base = nrun, g.info holding 10 words -- and the runs.  runs: the
 // descriptors on the device; rf: the exclusive scan of their nent (nrun + 1);
 // nent = rf[nrun]; rok: every run entry's order key.  Per query: res (the
 // results, scratch until the error words are back), len (its answered length,
@@ -172,8 +172,10 @@ struct GetArgs {
 // value's address).  g.info[5] = the first run entry refused (atomic min, set
 // to ~0 by the caller), [6] the queries a run answered (set to 0), [7] the
 // gathered bytes, [8] the pairs an opened set's fences dropped (set to 0;
-// lsmck_tableset.hip, whose table arrays lie in the set and not in scratch).
+// lsmck_tableset.hip, whose table arrays lie in the set and not in scratch),
+// [9] those its filters dropped behind the fences (set to 0).
 namespace ts { struct Fence; }
+namespace blm { struct Desc; }
 struct DbArgs {
   GetArgs g;
   const lsmck_get_run* runs;
@@ -201,7 +203,17 @@ int lsmk_get_pairs(const lsmck::GetArgs* a, hipStream_t st);    // every (query,
 int lsmk_get_resolve(const lsmck::GetArgs* a, lsmck_get_result* res, hipStream_t st);
 // opened table set (lsmck_tableset.hip)
 int lsmk_ts_fences(const lsmck::GetArgs* a, lsmck::ts::Fence* fence, uint32_t cap, hipStream_t st);  // behind lsmk_get_index
-int lsmk_ts_pairs(const lsmck::GetArgs* a, const lsmck::ts::Fence* fence, hipStream_t st);  // lsmk_get_pairs behind the fences
+// lsmk_get_pairs behind the fences and, with desc, the filters (filt, and qh from lsmk_ts_hash; info[9] = the pairs they drop)
+int lsmk_ts_pairs(const lsmck::GetArgs* a, const lsmck::ts::Fence* fence, const lsmck::blm::Desc* desc, const uint32_t* filt,
+                  const uint64_t* qh, hipStream_t st);
+// ... its filters ("bloom_bits" > 0; lanes = the set's items + its tables): count, sizes (info[5..7]), fill; a get's hashes
+int lsmk_ts_bloom_count(const lsmck::GetArgs* a, uint64_t lanes, uint32_t cap, unsigned long long* nkeys, uint32_t* over,
+                        hipStream_t st);
+int lsmk_ts_bloom_size(uint64_t ntab, uint32_t bits, const unsigned long long* nkeys, const uint32_t* over,
+                       lsmck::blm::Desc* desc, unsigned long long* info, hipStream_t st);
+int lsmk_ts_bloom_fill(const lsmck::GetArgs* a, uint64_t lanes, uint32_t cap, const lsmck::blm::Desc* desc, uint32_t* filt,
+                       hipStream_t st);
+int lsmk_ts_hash(const lsmck::GetArgs* a, uint64_t* qh, hipStream_t st);
 // batch SSTable decode and merge (lsmck_sstmerge.hip); ntab > 0 and n > 0
 int lsmk_dec_index(const lsmck::DecArgs* a, hipStream_t st);     // spans, index parse, segment starts
 int lsmk_dec_segments(const lsmck::DecArgs* a, hipStream_t st);  // the segments' check

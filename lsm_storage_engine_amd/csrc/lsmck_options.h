@@ -41,6 +41,8 @@ struct Options {
   long cut_walk_cap = 4096, cut_block = 8192;
   // the opened table set: the records a fence's walk visits at most (lsmck_tableset.h; read when a set is opened)
   long fence_walk_cap = 256;
+  // ... and the bits per key of its tables' resident bloom filters, 0: none (lsmck_bloom.h; read when a set is opened)
+  long bloom_bits = 0;
 };
 
 // `variant` bits
@@ -144,6 +146,7 @@ constexpr OptionRow kPlanOptions[] = {
 // the opened table set's (lsmck_tableset_open), looked up behind kPlanOptions
 constexpr OptionRow kSetOptions[] = {
     LSMCK_OPT(fence_walk_cap, 1, 1l << 20),
+    LSMCK_OPT(bloom_bits, 4, 64, true),
 };
 #undef LSMCK_OPT
 

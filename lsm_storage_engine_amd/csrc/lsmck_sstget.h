@@ -21,10 +21,11 @@
 //     it, or data_len; scan_range (datafile.rs:85-103) reads the record at
 //     start even when start >= end, returns it when its key is the key, else
 //     advances and stops once pos >= end or no whole record fits.
-// read_record is mrg::rec_at.  The bloom filter (sstable.rs:98) is not read: a
-// filter built from the table's own keys has no false negatives, so it never
-// changes a result, only the work; the bloom file is out of scope here as
-// everywhere in this project.
+// read_record is mrg::rec_at.  The bloom filter (sstable.rs:98) has no part in
+// these calls: a filter built from the table's own keys has no false negatives,
+// so it never changes a result, only the work.  An opened table set keeps such
+// filters on the device ("bloom_bits", lsmck_bloom.h); the reference's bloom
+// file is out of scope here as everywhere in this project.
 //
 // The device form keeps per item of every table one order key (mrg::OKey), its
 // offset in the index arena and its position, so that a probe of the lower

@@ -103,9 +103,12 @@ class Reader:
     them: ``levels``' files are read once and opened as one
     lsmck_tableset_open set on ``ctx`` -- the index pass and the tables' key
     fences stay on the device -- and ``get_many`` is one
-    lsmck_tableset_get_batch call.  ``close()`` frees the set."""
+    lsmck_tableset_get_batch call.  ``bloom_bits`` > 0 (4..64) also keeps a
+    resident bloom filter per table at that many bits per key (the option
+    "bloom_bits" is set around the open and restored).  ``close()`` frees the
+    set."""
 
-    def __init__(self, levels, ctx):
+    def __init__(self, levels, ctx, bloom_bits=0):
         order = [m for level in levels for m in reversed(level)]
         datas = [open(m.data_path(), "rb").read() for m in order]
         idxs = [open(m.index_path(), "rb").read() for m in order]
@@ -113,8 +116,13 @@ class Reader:
         spans["data_len"], spans["index_len"] = [len(d) for d in datas], [len(x) for x in idxs]
         spans["data_off"] = np.cumsum(spans["data_len"]) - spans["data_len"]
         spans["index_off"] = np.cumsum(spans["index_len"]) - spans["index_len"]
-        self.set = ctx.tableset_open(np.frombuffer(b"".join(datas), np.uint8), np.frombuffer(b"".join(idxs), np.uint8),
-                                     spans)
+        before = ctx.get_stat("bloom_bits")
+        ctx.set_option("bloom_bits", bloom_bits)
+        try:
+            self.set = ctx.tableset_open(np.frombuffer(b"".join(datas), np.uint8),
+                                         np.frombuffer(b"".join(idxs), np.uint8), spans)
+        finally:
+            ctx.set_option("bloom_bits", before)
 
     def get_many(self, memtables, keys, internal=False):
         """``get_many(memtables, levels, keys, ctx, internal)`` over the opened tables: the same answers."""

@@ -219,7 +219,9 @@ class TableSet:
             pass
 
     def stat(self, key):
-        """lsmck_tableset_stat: "tables", "items", "fenced_low", "fenced_high", "resident_bytes"."""
+        """lsmck_tableset_stat: "tables", "items", "fenced_low", "fenced_high",
+        "resident_bytes", and of a set opened with "bloom_bits" > 0 "bloom_tables",
+        "bloom_keys" and "bloom_bytes" (0 otherwise)."""
         v = C.c_long()
         _lib.check(self.ctx.lib.lsmck_tableset_stat(self.handle, key.encode(), C.byref(v)), f"tableset_stat({key})")
         return v.value

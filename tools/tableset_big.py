@@ -19,7 +19,15 @@ pairs fenced / looked up / walked, and the two comparisons:
   one   set probe  <= yardstick probe + yardstick spread           ("no_worse")
 The results of the two calls are compared byte for byte.
 
-  python3 tools/tableset_big.py [--log2 22] [--order 256] [--reps 3] [--out profiles/r14/tableset/tableset_big.json]
+--bloom-bits B (4..64) adds, per shape, a second set opened with "bloom_bits" B
+beside the one opened with 0: the open's stages with the filters' own
+("tableset_open_bloom_ns"), then the two sets' gets alternating in the same
+process -- probe and resolve times, the pairs fenced / bloomed / looked up /
+walked of each -- and the two results compared byte for byte ("bloom" in the
+JSON).
+
+  python3 tools/tableset_big.py [--log2 22] [--order 256] [--reps 3] [--bloom-bits 12]
+                                [--out profiles/r14/tableset/tableset_big.json]
 """
 import argparse
 import json
@@ -48,7 +56,66 @@ def spread(v):
     return round(float(max(v) - min(v)), 3)
 
 
-def shape(ctx, name, ntab, m, nq, kmax, reps):
+def bloom_part(ctx, name, ts, reps, bits, open_args, get_args, dres, dres3, nq, ntab):
+    """The set opened with ``bits`` per key beside ``ts`` (opened with 0): open stages, alternating gets, counts."""
+    ctx.set_option("sst_encode_time", 1)
+    ctx.set_option("bloom_bits", bits)
+    opens, stage = [], {"index": [], "fence": [], "bloom": []}
+    tb = None
+    try:
+        for r in range(reps + 1):
+            if tb is not None:
+                tb.close()
+            t0 = time.perf_counter()
+            tb = ctx.tableset_open(*open_args[0], **open_args[1])
+            dt = (time.perf_counter() - t0) * 1e3
+            if r:
+                opens.append(dt)
+                for s in stage:
+                    stage[s].append(ctx.get_stat(f"tableset_open_{s}_ns") / 1e6)
+    finally:
+        ctx.set_option("bloom_bits", 0)
+    out = {"bits": bits, "open_ms": med(opens), "open_spread_ms": spread(opens),
+           "open_stage_ms": {s: med(v) for s, v in stage.items()},
+           "set": {k: tb.stat(k) for k in ("bloom_tables", "bloom_keys", "bloom_bytes", "resident_bytes")}}
+    names = ("fenced", "bloomed", "probed", "walked")
+    times = {0: {s: [] for s in SET}, bits: {s: [] for s in SET}}
+    whole, counts = {0: [], bits: []}, {}
+    for r in range(reps + 1):
+        for b, s_, d_ in ((0, ts, dres), (bits, tb, dres3)):
+            t0 = time.perf_counter()
+            s_.get_batch_device(*get_args, d_.ptr)
+            dt = (time.perf_counter() - t0) * 1e3
+            st = {s: ctx.get_stat(f"tableset_{s}_ns") / 1e6 for s in SET}
+            counts[b] = {k: ctx.get_stat("tableset_" + k) for k in names}
+            print(f"{name} bloom {r}: bits {b}: set get {dt:.2f} ms {st} {counts[b]}", file=sys.stderr, flush=True)
+            if r:
+                whole[b].append(dt)
+                for s in SET:
+                    times[b][s].append(st[s])
+    ctx.set_option("sst_encode_time", 0)
+    plain = {0: [], bits: []}  # untimed: no events, no pair counters
+    for r in range(reps + 1):
+        for b, s_, d_ in ((0, ts, dres), (bits, tb, dres3)):
+            t0 = time.perf_counter()
+            s_.get_batch_device(*get_args, d_.ptr)
+            if r:
+                plain[b].append((time.perf_counter() - t0) * 1e3)
+    a, c = dres.download(_lib.GET_RESULT_DTYPE, nq), dres3.download(_lib.GET_RESULT_DTYPE, nq)
+    assert a.tobytes() == c.tobytes(), "the set with filters answers as the set without"
+    out["results_identical"] = True
+    for b, key in ((0, "without"), (bits, "with")):
+        out[key] = {"get_ms": med(whole[b]), "stage_ms": {s: med(v) for s, v in times[b].items()},
+                    "stage_spread_ms": {s: spread(v) for s, v in times[b].items()}, "pairs": counts[b],
+                    "uncounted_wall_ms": med(plain[b]), "uncounted_wall_spread_ms": spread(plain[b])}
+    p0, p1 = out["without"]["stage_ms"]["probe"], out["with"]["stage_ms"]["probe"]
+    out["probe_without_over_with"] = round(p0 / p1, 3) if p1 else None
+    out["bloomed_share_of_unfenced"] = round(counts[bits]["bloomed"] / max(1, nq * ntab - counts[bits]["fenced"]), 4)
+    tb.close()
+    return out
+
+
+def shape(ctx, name, ntab, m, nq, kmax, reps, bloom_bits=0):
     n = ntab * m
     rng = np.random.default_rng(0x6E7)
     ln = gen_zipf_lengths(0x5EED0003, n, kmax=kmax).astype(np.uint64)
@@ -163,6 +230,10 @@ def shape(ctx, name, ntab, m, nq, kmax, reps):
     out["beats_index_plus_probe_by_more_than_spread"] = bool(p < med(yip) - spread(yip))
     out["no_worse_than_probe_within_spread"] = bool(p <= out["db_get_stage_ms"]["probe"] + spread(yard["probe"]))
     out["fence_test_ns_per_pair"] = round((p - out["db_get_stage_ms"]["probe"]) * 1e6 / (nq * ntab), 4)
+    if bloom_bits:
+        out["bloom"] = bloom_part(ctx, name, ts, reps, bloom_bits,
+                                  ((ddata.ptr, dindex.ptr, dspans.ptr), dict(ntab=ntab, data_bytes=db, index_bytes=ib)),
+                                  ([], dqk.ptr, qkeys.nbytes, dq.ptr, nq), dres2, dres, nq, ntab)
     ts.close()
     for buf in (ddata, dindex, dspans, dqk, dq, dres, dres2):
         buf.free()
@@ -176,13 +247,14 @@ def main():
     ap.add_argument("--queries", type=int, default=1 << 20)
     ap.add_argument("--kmax", type=int, default=64, help="Zipf lengths on k = 1..kmax (L = 64k - j)")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--bloom-bits", type=int, default=0, help="also a set opened with this many filter bits per key (4..64)")
     ap.add_argument("--out", default=os.path.join("profiles", "r14", "tableset", "tableset_big.json"))
     a = ap.parse_args()
     ctx = Context(0)
     out = {"metric": "gets over an opened table set beside lsmck_db_get_batch (stage times between device events)",
            "kmax": a.kmax, "reps": a.reps,
-           "many": shape(ctx, "many", a.order, 1024, a.queries, a.kmax, a.reps),
-           "one": shape(ctx, "one", 4, 1 << a.log2, a.queries, a.kmax, a.reps)}
+           "many": shape(ctx, "many", a.order, 1024, a.queries, a.kmax, a.reps, a.bloom_bits),
+           "one": shape(ctx, "one", 4, 1 << a.log2, a.queries, a.kmax, a.reps, a.bloom_bits)}
     line = json.dumps(out)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
