@@ -396,6 +396,13 @@ int lsmck_ctx_set_option(lsmck_ctx* ctx, const char* key, long value);
  *                    prev; the walk; the blocks' exits and the chain; the
  *                    marks, the segment numbers and the entry flags; the sort
  *                    by segment and the outputs.
+ *   "apply_gets", "apply_misses"  the Gets of the last lsmck_db_apply_plan and
+ *                    those no write of its stream answers (the three keys
+ *                    above are set by it as well).
+ *   "apply_order_ns", "apply_prep_ns", "apply_walk_ns", "apply_chain_ns",
+ *   "apply_mark_ns", "apply_emit_ns"  DIAGNOSTIC, subject to change: the last
+ *                    lsmck_db_apply_plan's stages, with "mem_build_time" 1
+ *                    (named at that call).
  * Returns 0 and *value, or LSMCK_EINVAL for an unknown key. */
 int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value);
 
@@ -1093,7 +1100,8 @@ void lsmck_tableset_close(lsmck_tableset* set);
  * command ents[j] came from.
  * Not modelled: a replayed memtable in front of the stream, the tokio
  * engine's old_memtable, compact() behind a flush (lsm_storage.rs:74; it moves
- * no cut), the bloom file, reads between the writes.
+ * no cut), the bloom file.  Reads between the writes are
+ * lsmck_db_apply_plan's, below.
  * On the device (lsmck_writeplan.hip, lsmck_writeplan.h): the memtable
  * build's rounds order the commands by (key, log position); from that every
  * command's predecessor with the same key.  A thread per candidate start
@@ -1134,6 +1142,96 @@ int lsmck_db_write_plan_cpu(const uint8_t* keys, size_t keys_bytes, const uint8_
                             lsmck_wal_cmd* ents, size_t ent_cap, uint32_t* src,
                             lsmck_write_seg* segs, size_t seg_cap,
                             size_t* nent, size_t* nflush, uint64_t* bad_index);
+
+/* Batch command stream: lsmck_db_write_plan with Gets between the writes --
+ * the commands of src/command.rs in arrival order, every get seeing every
+ * write before it (LsmStorage::get, src/sync/lsm_storage.rs:99-125).  Commands
+ * 0..n-1 have type 1 Insert (an update is an Insert, lsm_storage.rs:128),
+ * 2 delete or LSMCK_CMD_GET; arenas and ranges as in lsmck_db_write_plan, a
+ * Get's val_off and vlen are not looked at.  They are applied in order to an
+ * LsmStorage whose memtable is empty, whose compact() is deferred and whose
+ * tables -- "the base" -- are the caller's.
+ * Writes.  lsmck_db_write_plan's rules, word for word.  A Get changes
+ * nothing: it adds no bytes and never flushes; it counts as a command in
+ * first_cmd (and towards "cut_walk_cap").  With every Get removed and the
+ * indices renumbered, ents, *nent, *nflush, mem_bytes and first_ent are
+ * lsmck_db_write_plan's output on the remaining commands, src and first_cmd
+ * the same after renumbering; a stream without Gets yields byte-identical
+ * outputs.  One new shape: the open segment may hold only Gets (a stream of
+ * Gets, or Gets behind a final flush): first_cmd < n, no entries, first_ent =
+ * *nent, mem_bytes = 0.
+ * Gets.  The reference asks the memtable, then level 0 newest first, then the
+ * lower levels; the stream's flushes are pushed behind the base's level-0
+ * tables, so they are met first, newest first, and a table written by
+ * from_memtable finds exactly the keys it holds.  So the Get at command i is
+ * answered by the last write j < i with its key, if there is one: by the
+ * memtable when j lies in i's segment (source = LSMCK_APPLY_MEMTABLE), else
+ * by the table that j's segment g was flushed to (source = g).  The answer is
+ * that write's value in vals: val_off / vlen of an Insert (val_off = 0 for an
+ * empty value), tomb_off and 1 for a delete; a delete, or an Insert of the
+ * single byte 0, carries LSMCK_GET_TOMBSTONE in bit 63 of val_off (Db::get's
+ * rule, as in lsmck_get_result).  With no such write the Get is a miss: source
+ * = LSMCK_GET_NONE, val_off = 0, vlen = 0, src_cmd = 0xFFFFFFFF, and the base
+ * answers it.
+ * gets[0 .. *nget) holds the Gets in stream order.  miss_q / miss_get
+ * (optional: both or both NULL, get_cap items each) hold the misses in stream
+ * order: {key_off, klen, 0} into keys, and the miss's index in gets -- queries
+ * of lsmck_tableset_get_batch or lsmck_db_get_batch with qkeys = keys.  *nmiss
+ * is reported also without them.
+ * On the device (lsmck_apply.hip, lsmck_apply.h): the write plan's kernels but
+ * four pieces that look at a key's run of the order, where Gets now stand
+ * between the writes -- the validation; prev, a write's previous *write*,
+ * which also answers a Get, from two max-scans over the order (the run's
+ * start, the last write); the entry flags, every write clearing the previous
+ * write of its (segment, key); and the Gets' and misses' slots from two scans
+ * over the stream.
+ * Flags, alignment (gets and miss_q 8-byte aligned, miss_get 4), synchrony,
+ * scratch and the 2^32 limit: lsmck_db_write_plan's; the host form stages the
+ * value arena whole.  nent, nflush, nget and nmiss must not be NULL.
+ * Returns 0 (n == 0: one open segment {0, 0, 0}, all counts 0), or
+ *   LSMCK_EINVAL  as lsmck_db_write_plan, in its order: the type check takes
+ *                 1, 2 and 3, a Get's key range is checked like any key, the
+ *                 entry-length and tombstone-byte rules hold for writes only.
+ *   LSMCK_ENOSPC  ent_cap < *nent, seg_cap < *nflush + 1 or get_cap < *nget:
+ *                 all four counts are the ones needed.
+ *   LSMCK_ENODEV  there is no GPU (and so no context).
+ * On any error no byte of any output array is written.
+ * lsmck_ctx_get_stat: "cut_steps", "cut_long" and "mem_rounds" as for the
+ * write plan, "apply_gets" and "apply_misses" for the last stream; with
+ * "mem_build_time" 1 the last call's stages between device events:
+ * "apply_order_ns" (validation and the rounds), "apply_prep_ns" (the packed
+ * words, both scans, prev), "apply_walk_ns", "apply_chain_ns", "apply_mark_ns"
+ * (the marks, the entry flags, the slots' scans) and "apply_emit_ns" (the
+ * Gets, the entries, the segments).
+ * Not modelled: a memtable that holds entries in front of the stream, the
+ * tokio engine's old_memtable, compact() behind a flush (it can resurrect a
+ * deleted key through the merge's tombstone drop), gathering the answers into
+ * a packed arena, merging the base's answers into gets. */
+#define LSMCK_CMD_GET 3u
+#define LSMCK_APPLY_MEMTABLE 0xFFFFFFFEu
+typedef struct {
+  uint64_t val_off;  /* in vals; bit 63 LSMCK_GET_TOMBSTONE; 0 for an empty value and for a miss */
+  uint32_t vlen;
+  uint32_t source;   /* LSMCK_APPLY_MEMTABLE, the flushed table (segment number), or LSMCK_GET_NONE */
+  uint32_t cmd;      /* the Get's index in cmds */
+  uint32_t src_cmd;  /* the write that answers, 0xFFFFFFFF for a miss */
+} lsmck_apply_get;   /* 24 bytes */
+int lsmck_db_apply_plan(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes, const uint8_t* vals, size_t vals_bytes,
+                        const lsmck_wal_cmd* cmds, size_t n, uint64_t limit, uint64_t tomb_off,
+                        lsmck_wal_cmd* ents, size_t ent_cap, uint32_t* src,
+                        lsmck_write_seg* segs, size_t seg_cap,
+                        lsmck_apply_get* gets, size_t get_cap, lsmck_get_query* miss_q, uint32_t* miss_get,
+                        size_t* nent, size_t* nflush, size_t* nget, size_t* nmiss, uint64_t* bad_index,
+                        unsigned flags);
+
+/* Host helper, no GPU: the same call on one thread with a std::map, host
+ * pointers only.  The same results and errors (no LSMCK_ENODEV). */
+int lsmck_db_apply_plan_cpu(const uint8_t* keys, size_t keys_bytes, const uint8_t* vals, size_t vals_bytes,
+                            const lsmck_wal_cmd* cmds, size_t n, uint64_t limit, uint64_t tomb_off,
+                            lsmck_wal_cmd* ents, size_t ent_cap, uint32_t* src,
+                            lsmck_write_seg* segs, size_t seg_cap,
+                            lsmck_apply_get* gets, size_t get_cap, lsmck_get_query* miss_q, uint32_t* miss_get,
+                            size_t* nent, size_t* nflush, size_t* nget, size_t* nmiss, uint64_t* bad_index);
 
 /* Whole-tree SSTable verify: the batch form of Checksums::verify over many
  * tables (Db::load, src/tokio/db.rs:37-59 -> src/tokio/sstable.rs:34).

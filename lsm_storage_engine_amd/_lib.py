@@ -106,6 +106,11 @@ assert GET_RUN_DTYPE.itemsize == 48
 # include/lsmck.h lsmck_write_seg (24 bytes, no padding): one segment of lsmck_db_write_plan
 WRITE_SEG_DTYPE = np.dtype([("first_cmd", "<u8"), ("first_ent", "<u8"), ("mem_bytes", "<u8")])
 assert WRITE_SEG_DTYPE.itemsize == 24
+# include/lsmck.h lsmck_apply_get (24 bytes, no padding): one Get of lsmck_db_apply_plan
+APPLY_GET_DTYPE = np.dtype([("val_off", "<u8"), ("vlen", "<u4"), ("source", "<u4"), ("cmd", "<u4"), ("src_cmd", "<u4")])
+assert APPLY_GET_DTYPE.itemsize == 24
+CMD_GET = 3  # LSMCK_CMD_GET: lsmck_wal_cmd.type of a Get in lsmck_db_apply_plan's stream
+APPLY_MEMTABLE = 0xFFFFFFFE  # LSMCK_APPLY_MEMTABLE: lsmck_apply_get.source when the memtable answered
 
 
 class TreeReport(C.Structure):
@@ -186,6 +191,12 @@ SIGNATURES = [
       C.c_uint]),
     ("lsmck_db_write_plan_cpu", C.c_int,  # the same call on the host, without context and flags
      [vp, sz, vp, sz, vp, sz, C.c_uint64, C.c_uint64, vp, sz, vp, vp, sz, C.POINTER(sz), C.POINTER(sz), u64p]),
+    ("lsmck_db_apply_plan", C.c_int,  # ... and gets: lsmck_apply_get[get_cap]; miss_q, miss_get: get_cap or NULL
+     [vp, vp, sz, vp, sz, vp, sz, C.c_uint64, C.c_uint64, vp, sz, vp, vp, sz, vp, sz, vp, vp, C.POINTER(sz),
+      C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), u64p, C.c_uint]),
+    ("lsmck_db_apply_plan_cpu", C.c_int,  # the same call on the host, without context and flags
+     [vp, sz, vp, sz, vp, sz, C.c_uint64, C.c_uint64, vp, sz, vp, vp, sz, vp, sz, vp, vp, C.POINTER(sz), C.POINTER(sz),
+      C.POINTER(sz), C.POINTER(sz), u64p]),
     ("lsmck_checksums_verify_many", C.c_int,
      [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), sz, C.POINTER(C.c_int)]),
     ("lsmck_tree_verify", C.c_int, [vp, C.c_char_p, C.POINTER(TreeReport)]),

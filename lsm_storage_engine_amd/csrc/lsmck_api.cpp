@@ -440,6 +440,19 @@ struct lsmck_ctx {
   } wp;
   StageTimer wp_timer;  // "mem_build_time" (this call too): order, walk, chain, mark, emit
   long cut_steps = 0, cut_long = 0;  // the last plan's walk steps and LONG memtables
+  // batch command stream (lsmck_device.h AplWs, laid over mem.ws as well; wp's
+  // buffers serve it too): the call's words -- the plan's [0..6], [7] the Gets,
+  // [8] the misses; the entries and the segments come back behind them -- and
+  // their pinned copy; host form: the Gets, the misses' queries and their Gets
+  struct {
+    DevBuf<unsigned long long> info;
+    PinBuf<unsigned long long> h_info;
+    DevBuf<lsmck_apply_get> gets;
+    DevBuf<lsmck_get_query> miss_q;
+    DevBuf<uint32_t> miss_get;
+  } ap;
+  StageTimer ap_timer;  // "mem_build_time" (this call too): order, prep, walk, chain, mark / flags / slots, gets / emit
+  long apply_gets = 0, apply_misses = 0;  // the last stream's Gets, and those no write of it answers
   // batch SSTable decode (lsmck_device.h DecArgs): the per-table and
   // per-segment scratch, the call's four words and their pinned copy; host
   // form: both images, the spans and the entries
@@ -1219,6 +1232,22 @@ int lsmck_ctx_get_stat(lsmck_ctx* ctx, const char* key, long* value) {
     *value = ctx->wp_timer.ns[3];
   } else if (!strcmp(key, "write_emit_ns")) {
     *value = ctx->wp_timer.ns[4];
+  } else if (!strcmp(key, "apply_gets")) {  // the last lsmck_db_apply_plan's Gets
+    *value = ctx->apply_gets;
+  } else if (!strcmp(key, "apply_misses")) {  // ... and those no write of the stream answers
+    *value = ctx->apply_misses;
+  } else if (!strcmp(key, "apply_order_ns")) {  // the last timed stream's stages ("mem_build_time")
+    *value = ctx->ap_timer.ns[0];
+  } else if (!strcmp(key, "apply_prep_ns")) {
+    *value = ctx->ap_timer.ns[1];
+  } else if (!strcmp(key, "apply_walk_ns")) {
+    *value = ctx->ap_timer.ns[2];
+  } else if (!strcmp(key, "apply_chain_ns")) {
+    *value = ctx->ap_timer.ns[3];
+  } else if (!strcmp(key, "apply_mark_ns")) {
+    *value = ctx->ap_timer.ns[4];
+  } else if (!strcmp(key, "apply_emit_ns")) {
+    *value = ctx->ap_timer.ns[5];
   } else {
     return lsmck_host::set_error(LSMCK_EINVAL, "unknown stat");
   }
@@ -2832,6 +2861,210 @@ int lsmck_db_write_plan(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes, 
   HIPCHK(hipStreamSynchronize(st));
   const int pair[5][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {5, 6}};
   for (int k = 0; k < 5; ++k) HIPCHK(T.span(pair[k][0], pair[k][1], k));
+  T.finish();
+  return 0;
+}
+
+// The write plan's body with the four pieces of lsmck_apply.hip in place of
+// lsmk_mem_validate / lsmk_wpl_check, lsmk_wpl_prep, wpl_flag and with the
+// Gets written behind the one read-back.  An open segment may hold no entry
+// here (only Gets): its first_ent is set before the emit, which writes it only
+// where a segment has an entry.
+int lsmck_db_apply_plan(lsmck_ctx* ctx, const uint8_t* keys, size_t keys_bytes, const uint8_t* vals, size_t vals_bytes,
+                        const lsmck_wal_cmd* cmds, size_t n, uint64_t limit, uint64_t tomb_off, lsmck_wal_cmd* ents,
+                        size_t ent_cap, uint32_t* src, lsmck_write_seg* segs, size_t seg_cap, lsmck_apply_get* gets,
+                        size_t get_cap, lsmck_get_query* miss_q, uint32_t* miss_get, size_t* nent, size_t* nflush,
+                        size_t* nget, size_t* nmiss, uint64_t* bad_index, unsigned flags) {
+  if (nent) *nent = 0;
+  if (nflush) *nflush = 0;
+  if (nget) *nget = 0;
+  if (nmiss) *nmiss = 0;
+  if (bad_index) *bad_index = ~0ull;
+  if (!nent || !nflush || !nget || !nmiss)
+    return lsmck_host::set_error(LSMCK_EINVAL, "apply plan: null nent, nflush, nget or nmiss");
+  if (flags & ~(LSMCK_DEVICE | LSMCK_HOST_PINNED)) return lsmck_host::set_error(LSMCK_EINVAL, "apply plan: unknown flag");
+  if ((miss_q == nullptr) != (miss_get == nullptr))
+    return lsmck_host::set_error(LSMCK_EINVAL, "apply plan: miss_q and miss_get are given both or neither");
+  if (n >= (1ull << 32))
+    return lsmck_host::set_error(LSMCK_EINVAL, "apply plan: more than 2^32-1 commands in one batch");
+  if (!ctx) return mem_no_ctx("apply plan");
+  int rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  DevGuard g(ctx->dev);
+  const hipStream_t st = ctx->stream0;
+  ScratchOrder so(ctx, st);
+  if (so.e != hipSuccess) return hip_error(so.e, "hipStreamWaitEvent(scratch)");
+  const bool dev = (flags & LSMCK_DEVICE) != 0;
+  if (n == 0) {  // the empty memtable, open
+    ctx->mem_rounds = ctx->cut_steps = ctx->cut_long = ctx->apply_gets = ctx->apply_misses = 0;
+    if (seg_cap < 1) return lsmck_host::set_error(LSMCK_ENOSPC, "apply plan: seg_cap is smaller than the segments");
+    if (!segs) return lsmck_host::set_error(LSMCK_EINVAL, "null segs");
+    if (dev) {
+      HIPCHK(hipMemsetAsync(segs, 0, sizeof(lsmck_write_seg), st));
+      HIPCHK(hipStreamSynchronize(st));
+    } else {
+      memset(segs, 0, sizeof(lsmck_write_seg));
+    }
+    return 0;
+  }
+  if (!cmds) return lsmck_host::set_error(LSMCK_EINVAL, "null commands");
+  auto& M = ctx->mem;
+  auto& Q = ctx->wp;
+  auto& A = ctx->ap;
+  const uint8_t *dk = keys, *dv = vals;
+  const lsmck_wal_cmd* dc = cmds;
+  // (apl_gets reads the one byte of an Insert of one byte: the host form stages the value arena too)
+  if (!dev && (rc = stage_inputs(ctx, &dk, keys_bytes, &dv, vals_bytes, true, &dc, n, st))) return rc;
+  const uint8_t* tomb = (vals && tomb_off < vals_bytes) ? dv + tomb_off : nullptr;  // null: it lies past the arena
+  const uint32_t cap = (uint32_t)ctx->opt.cut_walk_cap, block = (uint32_t)ctx->opt.cut_block;
+  const uint64_t nblk = (n + block - 1) / block;
+  const uint32_t ecap = (uint32_t)std::min<uint64_t>({nblk + n / cap + 3, (uint64_t)n + 1, 0xFFFFFFFFull});
+  lsmck::MemWs W;
+  lsmck::WplWs P;
+  lsmck::AplWs S;
+  if ((rc = M.ws.ensure(lsmk_mem_carve(nullptr, n, nullptr))) || (rc = M.info.ensure(4)) ||
+      (rc = M.h_info.ensure(8, -1)) || (rc = A.info.ensure(9)) || (rc = A.h_info.ensure(16, -1)) ||
+      (rc = Q.elist.ensure(ecap)) || (rc = Q.bfirst.ensure((size_t)nblk)))
+    return rc;
+  (void)lsmk_mem_carve(M.ws, n, &W);
+  StageTimer& T = ctx->ap_timer;
+  T.begin(ctx->opt.mem_build_time);
+  // 1. validate; the words come back before any kernel reads a key
+  unsigned long long* info = A.info;
+  HIPCHK(hipMemsetAsync(info, 0xFF, 8, st));
+  HIPCHK(hipMemsetAsync(info + 1, 0, 64, st));
+  HIPCHK(hipMemsetAsync(M.info + 1, 0, 8, st));
+  HIPCHK(T.mark(0, st));
+  if ((rc = lsmk_apl_validate(dc, n, keys_bytes, vals_bytes, tomb, info, st)))
+    return launch_rc(rc, "apply plan validate kernel");
+  HIPCHK(hipMemcpyAsync(A.h_info, info, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (A.h_info[0] != ~0ull) {
+    if (bad_index) *bad_index = A.h_info[0];
+    return lsmck_host::set_error(LSMCK_EINVAL, "apply plan: invalid command (type, source range or an entry too long)");
+  }
+  if (A.h_info[1])
+    return lsmck_host::set_error(LSMCK_EINVAL, "apply plan: a delete needs a 0 byte at vals[tomb_off]");
+  // ... the order: the memtable build's rounds (they read key ranges only)
+  if ((rc = lsmk_mem_init(&W, n, st))) return launch_rc(rc, "memtable init kernel");
+  unsigned group_bits = 1;
+  while (group_bits < 32 && ((uint64_t)1 << group_bits) < n) ++group_bits;
+  uint64_t m = n >= 2 ? n : 0;
+  long rounds = 0;
+  for (uint64_t r = 0; m; ++r, ++rounds) {
+    size_t tmp = 0;
+    if ((rc = lsmk_mem_sort_regroup(&W, m, r, group_bits, nullptr, &tmp, nullptr, st)))
+      return launch_rc(rc, "memtable sort (temporary storage size)");
+    if ((rc = M.tmp.ensure(tmp))) return rc;
+    if ((rc = lsmk_mem_chunk(&W, dk, dc, m, r, st))) return launch_rc(rc, "memtable chunk kernel");
+    tmp = M.tmp.cap();
+    if ((rc = lsmk_mem_sort_regroup(&W, m, r, group_bits, M.tmp, &tmp, M.info + 1, st)))
+      return launch_rc(rc, "memtable sort / regroup kernels");
+    HIPCHK(hipMemcpyAsync(M.h_info + 1, M.info + 1, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (M.h_info[1] > m) return lsmck_host::set_error(LSMCK_EIO, "apply plan: active count grew");
+    m = M.h_info[1];
+    std::swap(W.apos, W.apos2);
+  }
+  ctx->mem_rounds = rounds;
+  lsmk_wpl_carve(&W, &P);
+  lsmk_apl_carve(&W, &P, &S);
+  HIPCHK(T.mark(1, st));
+  // 2. prev, the answering writes, the packed words
+  size_t tmp = 0;
+  if ((rc = lsmk_apl_prep(&P, &S, dc, n, nullptr, &tmp, st))) return launch_rc(rc, "apply plan scans (size)");
+  if ((rc = M.tmp.ensure(tmp))) return rc;
+  tmp = M.tmp.cap();
+  if ((rc = lsmk_apl_prep(&P, &S, dc, n, M.tmp, &tmp, st))) return launch_rc(rc, "apply plan prep kernels");
+  HIPCHK(T.mark(2, st));
+  // 3. the walk  4. the chain  5. the marks, the segment numbers, the entry flags, the Gets' slots
+  if ((rc = lsmk_wpl_walk(&P, n, limit, cap, info + 2, st))) return launch_rc(rc, "write plan walk kernel");
+  HIPCHK(T.mark(3, st));
+  if ((rc = lsmk_wpl_chain(&P, n, block, limit, Q.elist, ecap, Q.bfirst, info + 3, st)))
+    return launch_rc(rc, "write plan chain kernels");
+  HIPCHK(T.mark(4, st));
+  size_t tmp2 = 0;
+  tmp = 0;
+  if ((rc = lsmk_wpl_number(&P, n, block, Q.elist, info + 3, Q.bfirst, nullptr, &tmp, st)) ||
+      (rc = lsmk_apl_flag(&P, &S, n, info, nullptr, &tmp2, st)))
+    return launch_rc(rc, "apply plan scans (size)");
+  if ((rc = M.tmp.ensure(std::max(tmp, tmp2)))) return rc;
+  tmp = M.tmp.cap();
+  if ((rc = lsmk_wpl_number(&P, n, block, Q.elist, info + 3, Q.bfirst, M.tmp, &tmp, st)))
+    return launch_rc(rc, "write plan mark kernels");
+  tmp = M.tmp.cap();
+  if ((rc = lsmk_apl_flag(&P, &S, n, info, M.tmp, &tmp, st))) return launch_rc(rc, "apply plan flag kernels");
+  HIPCHK(T.mark(5, st));
+  // the one read-back: the steps, the chain's words, the Gets, the misses, the entries, the segments
+  A.h_info[10] = A.h_info[11] = 0;
+  HIPCHK(hipMemcpyAsync(A.h_info + 2, info + 2, 56, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(A.h_info + 10, P.ex + n, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(A.h_info + 11, P.seg1 + (n - 1), 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  ctx->cut_steps = (long)A.h_info[2];
+  ctx->cut_long = (long)A.h_info[4];
+  if (A.h_info[6]) return lsmck_host::set_error(LSMCK_EIO, "apply plan: the chain's entry list overflowed");
+  const int closed = A.h_info[5] != 0;
+  const uint64_t ngets = A.h_info[7], misses = A.h_info[8], live = A.h_info[10], nseg = A.h_info[11];
+  // (every closed segment holds its flushing Insert; the open one may hold Gets alone)
+  if (nseg == 0 || live < (closed ? nseg : nseg - 1) || misses > ngets || ngets > n)
+    return lsmck_host::set_error(LSMCK_EIO, "apply plan: no segment found, or the counts disagree");
+  const uint64_t flushes = closed ? nseg : nseg - 1;
+  ctx->apply_gets = (long)ngets;
+  ctx->apply_misses = (long)misses;
+  *nent = (size_t)live;
+  *nflush = (size_t)flushes;
+  *nget = (size_t)ngets;
+  *nmiss = (size_t)misses;
+  if (ent_cap < live || seg_cap < flushes + 1 || get_cap < ngets)
+    return lsmck_host::set_error(LSMCK_ENOSPC, "apply plan: ent_cap, seg_cap or get_cap is smaller than the result");
+  if ((live && !ents) || !segs || (ngets && !gets)) return lsmck_host::set_error(LSMCK_EINVAL, "null ents, segs or gets");
+  lsmck_wal_cmd* de = ents;
+  uint32_t* ds = src;
+  lsmck_write_seg* dg = segs;
+  lsmck_apply_get* dq = gets;
+  lsmck_get_query* dmq = miss_q;
+  uint32_t* dmg = miss_get;
+  if (!dev) {
+    if ((rc = M.ents.ensure((size_t)live)) || (src && (rc = M.src.ensure((size_t)live))) ||
+        (rc = Q.segs.ensure((size_t)flushes + 1)) || (rc = A.gets.ensure((size_t)ngets)) ||
+        (miss_q && ((rc = A.miss_q.ensure((size_t)misses)) || (rc = A.miss_get.ensure((size_t)misses)))))
+      return rc;
+    de = M.ents;
+    ds = src ? M.src.get() : nullptr;
+    dg = Q.segs;
+    dq = A.gets;
+    dmq = miss_q ? A.miss_q.get() : nullptr;
+    dmg = miss_q ? A.miss_get.get() : nullptr;
+  }
+  tmp = 0;
+  if (live) {
+    if ((rc = lsmk_wpl_emit(&P, dc, n, live, nseg, closed, tomb_off, de, ds, dg, nullptr, &tmp, st)))
+      return launch_rc(rc, "write plan sort (temporary storage size)");
+    if ((rc = M.tmp.ensure(tmp))) return rc;
+  }
+  tmp = M.tmp.cap();
+  HIPCHK(T.mark(6, st));
+  // 6. the Gets (before the emit's sort takes the misses' slots' array), then the entries and the segments
+  if (ngets && (rc = lsmk_apl_gets(&P, &S, dc, dv, n, tomb_off, dq, dmq, dmg, st)))
+    return launch_rc(rc, "apply plan gets kernel");
+  if (!closed && (rc = lsmk_apl_open_seg(dg, nseg - 1, live, st))) return launch_rc(rc, "apply plan open segment kernel");
+  if (live && (rc = lsmk_wpl_emit(&P, dc, n, live, nseg, closed, tomb_off, de, ds, dg, M.tmp, &tmp, st)))
+    return launch_rc(rc, "write plan emit kernels");
+  HIPCHK(T.mark(7, st));
+  if (!dev) {
+    if (live) HIPCHK(hipMemcpyAsync(ents, de, (size_t)live * sizeof(lsmck_wal_cmd), hipMemcpyDeviceToHost, st));
+    if (src && live) HIPCHK(hipMemcpyAsync(src, ds, (size_t)live * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(segs, dg, ((size_t)flushes + 1) * sizeof(lsmck_write_seg), hipMemcpyDeviceToHost, st));
+    if (ngets) HIPCHK(hipMemcpyAsync(gets, dq, (size_t)ngets * sizeof(lsmck_apply_get), hipMemcpyDeviceToHost, st));
+    if (miss_q && misses) {
+      HIPCHK(hipMemcpyAsync(miss_q, dmq, (size_t)misses * sizeof(lsmck_get_query), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(miss_get, dmg, (size_t)misses * 4, hipMemcpyDeviceToHost, st));
+    }
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  const int pair[6][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {4, 5}, {6, 7}};
+  for (int k = 0; k < 6; ++k) HIPCHK(T.span(pair[k][0], pair[k][1], k));
   T.finish();
   return 0;
 }

@@ -26,6 +26,7 @@
 #include "lsmck_sstget.h"
 #include "lsmck_sstmerge.h"
 #include "lsmck_writeplan.h"
+#include "lsmck_apply.h"
 
 #if defined(__x86_64__)
 #include <cpuid.h>
@@ -598,6 +599,112 @@ int lsmck_db_write_plan_cpu(const uint8_t* keys, size_t keys_bytes, const uint8_
     if (src) src[j] = order[j];
   }
   memcpy(segs, sg.data(), sg.size() * sizeof(lsmck_write_seg));
+  return 0;
+}
+
+// lsmck_db_apply_plan on one thread: lsmck_db_write_plan_cpu's loop, a Get
+// changing nothing, and beside the memtable's map one over the whole stream:
+// every key's last write and the segment it lies in -- what answers a Get
+// (lsmck_apply.h); the checks and the answer are the device's
+int lsmck_db_apply_plan_cpu(const uint8_t* keys, size_t keys_bytes, const uint8_t* vals, size_t vals_bytes,
+                            const lsmck_wal_cmd* cmds, size_t n, uint64_t limit, uint64_t tomb_off,
+                            lsmck_wal_cmd* ents, size_t ent_cap, uint32_t* src, lsmck_write_seg* segs, size_t seg_cap,
+                            lsmck_apply_get* gets, size_t get_cap, lsmck_get_query* miss_q, uint32_t* miss_get,
+                            size_t* nent, size_t* nflush, size_t* nget, size_t* nmiss, uint64_t* bad_index) {
+  namespace W = lsmck::wpl;
+  namespace A = lsmck::apl;
+  if (nent) *nent = 0;
+  if (nflush) *nflush = 0;
+  if (nget) *nget = 0;
+  if (nmiss) *nmiss = 0;
+  if (bad_index) *bad_index = ~0ull;
+  if (!nent || !nflush || !nget || !nmiss)
+    return lsmck_host::set_error(LSMCK_EINVAL, "apply plan: null nent, nflush, nget or nmiss");
+  if ((miss_q == nullptr) != (miss_get == nullptr))
+    return lsmck_host::set_error(LSMCK_EINVAL, "apply plan: miss_q and miss_get are given both or neither");
+  if (n >= (1ull << 32))
+    return lsmck_host::set_error(LSMCK_EINVAL, "apply plan: more than 2^32-1 commands in one batch");
+  if (n && !cmds) return lsmck_host::set_error(LSMCK_EINVAL, "null commands");
+  bool deletes = false;
+  for (size_t i = 0; i < n; ++i) {
+    if (!A::valid(cmds[i], keys_bytes, vals_bytes) || !A::fits(cmds[i])) {
+      if (bad_index) *bad_index = i;
+      return lsmck_host::set_error(LSMCK_EINVAL, "apply plan: invalid command (type, source range or an entry too long)");
+    }
+    deletes |= cmds[i].type == 2u;
+  }
+  if (deletes && (!vals || W::tomb_bad(vals, vals_bytes, tomb_off)))
+    return lsmck_host::set_error(LSMCK_EINVAL, "apply plan: a delete needs a 0 byte at vals[tomb_off]");
+  struct Key {
+    const uint8_t* p;
+    uint32_t len;
+    bool operator<(const Key& o) const {
+      const uint32_t m = len < o.len ? len : o.len;
+      const int c = m ? memcmp(p, o.p, m) : 0;
+      return c ? c < 0 : len < o.len;
+    }
+  };
+  std::map<Key, uint32_t> table;  // the key's last writer in the current memtable
+  std::map<Key, uint32_t> last;   // ... in the stream so far
+  std::vector<uint32_t> seg1(n);  // a command's segment number plus one
+  std::vector<uint32_t> order;
+  std::vector<lsmck_write_seg> sg;
+  std::vector<lsmck_apply_get> gs;
+  std::vector<uint32_t> mg;
+  uint64_t bytes = 0, first_cmd = 0;
+  auto close = [&](uint64_t next_cmd) {
+    lsmck_write_seg s;
+    s.first_cmd = first_cmd, s.first_ent = order.size(), s.mem_bytes = bytes;
+    sg.push_back(s);
+    for (const auto& kv : table) order.push_back(kv.second);
+    table.clear();
+    bytes = 0;
+    first_cmd = next_cmd;
+  };
+  for (size_t i = 0; i < n; ++i) {
+    const lsmck_wal_cmd& c = cmds[i];
+    const Key k{c.klen ? keys + c.key_off : nullptr, c.klen};
+    seg1[i] = (uint32_t)sg.size() + 1u;
+    if (A::is_get(c)) {
+      const auto it = last.find(k);
+      const uint32_t j = it == last.end() ? A::kNone : it->second;
+      if (j == A::kNone) mg.push_back((uint32_t)gs.size());
+      gs.push_back(A::answer(cmds, vals, tomb_off, (uint32_t)i, j,
+                             j == A::kNone ? LSMCK_GET_NONE : A::source(seg1.data(), (uint32_t)i, j)));
+      continue;
+    }
+    last[k] = (uint32_t)i;
+    auto it = table.find(k);
+    if (it != table.end()) {
+      bytes -= W::a_of(W::pack(cmds[it->second]));
+      it->second = (uint32_t)i;
+    } else {
+      table.emplace(k, (uint32_t)i);
+    }
+    bytes += W::a_of(W::pack(c));
+    if (c.type == 1u && bytes >= limit) close(i + 1);
+  }
+  const size_t flushes = sg.size();
+  close(n);  // the open segment
+  *nent = order.size();
+  *nflush = flushes;
+  *nget = gs.size();
+  *nmiss = mg.size();
+  if (ent_cap < order.size() || seg_cap < flushes + 1 || get_cap < gs.size())
+    return lsmck_host::set_error(LSMCK_ENOSPC, "apply plan: ent_cap, seg_cap or get_cap is smaller than the result");
+  if ((order.size() && !ents) || !segs || (gs.size() && !gets))
+    return lsmck_host::set_error(LSMCK_EINVAL, "null ents, segs or gets");
+  for (size_t j = 0; j < order.size(); ++j) {
+    ents[j] = W::entry(cmds[order[j]], tomb_off);
+    if (src) src[j] = order[j];
+  }
+  memcpy(segs, sg.data(), sg.size() * sizeof(lsmck_write_seg));
+  if (!gs.empty()) memcpy(gets, gs.data(), gs.size() * sizeof(lsmck_apply_get));
+  if (miss_q)
+    for (size_t m = 0; m < mg.size(); ++m) {
+      miss_q[m] = A::miss_query(cmds[gs[mg[m]].cmd]);
+      miss_get[m] = mg[m];
+    }
   return 0;
 }
 

@@ -95,6 +95,19 @@ struct WplWs {
   uint8_t *head, *state;
 };
 
+// The batch command stream's own arrays (lsmck_apply.hip; lsmk_apl_carve lays
+// them over what the write plan leaves free at the time).  ans: per command,
+// the last write before it with its key -- what answers a Get -- in the one
+// array of the workspace the plan never uses (apos2).  During prep, over the
+// entry arrays that the emit fills much later: eh / rs and ew / lw (the two
+// scans' inputs and outputs per position of the order), then pq over eh (per
+// position: the position of that write; read by the entry flags).  Behind the
+// marks, over the walk's arrays: gf / mf (per command: it is a Get; it is a
+// miss) and their exclusive scans gslot / mslot.
+struct AplWs {
+  uint32_t *ans, *eh, *rs, *ew, *lw, *pq, *gf, *mf, *gslot, *mslot;
+};
+
 // The batch SSTable decode's arguments and scratch (lsmck_sstmerge.hip dec_*).
 // Per table: segfirst (its hint's items, then their exclusive scan: its place
 // in segpos; ntab + 1), state / fail (lsmck_sstmerge.hip kDec*; bit 0 of fail:
@@ -255,6 +268,29 @@ int lsmk_wpl_mark(const lsmck::WplWs* P, uint64_t n, uint32_t block, const uint3
 int lsmk_wpl_emit(const lsmck::WplWs* P, const lsmck_wal_cmd* cmds, uint64_t n, uint64_t nent, uint64_t nseg,
                   int closed, uint64_t tomb_off, lsmck_wal_cmd* ents, uint32_t* src, lsmck_write_seg* segs, void* tmp,
                   size_t* tmp_bytes, hipStream_t st);
+int lsmk_wpl_number(const lsmck::WplWs* P, uint64_t n, uint32_t block, const uint32_t* elist,
+                    const unsigned long long* cinfo, const uint32_t* bfirst, void* tmp, size_t* tmp_bytes,
+                    hipStream_t st);
+// batch command stream (lsmck_db_apply_plan; lsmck_apply.hip apl_*): the four
+// pieces that replace the write plan's where Gets stand between the writes.
+// info: 9 words -- [0] the first command refused (atomic min, set to ~0 by the
+// caller), [1] the tombstone byte is bad (set to 0), [7] the Gets, [8] the misses
+// (written behind the slots' scans; [2..6] are the walk's and the chain's)
+void lsmk_apl_carve(const lsmck::MemWs* W, const lsmck::WplWs* P, lsmck::AplWs* A);
+int lsmk_apl_validate(const lsmck_wal_cmd* cmds, uint64_t n, uint64_t keys_bytes, uint64_t vals_bytes,
+                      const uint8_t* tomb, unsigned long long* info, hipStream_t st);
+// aw and mark, then prev, ans, pq and the writes as act (n + 1).  tmp == nullptr: *tmp_bytes alone
+int lsmk_apl_prep(const lsmck::WplWs* P, const lsmck::AplWs* A, const lsmck_wal_cmd* cmds, uint64_t n, void* tmp,
+                  size_t* tmp_bytes, hipStream_t st);
+// behind lsmk_wpl_number: the entry flags and their slots (ex[n] = the entries), the Gets' and the misses' slots
+int lsmk_apl_flag(const lsmck::WplWs* P, const lsmck::AplWs* A, uint64_t n, unsigned long long* info, void* tmp,
+                  size_t* tmp_bytes, hipStream_t st);
+// gets, and miss_q / miss_get (both or neither)
+int lsmk_apl_gets(const lsmck::WplWs* P, const lsmck::AplWs* A, const lsmck_wal_cmd* cmds, const uint8_t* vals,
+                  uint64_t n, uint64_t tomb_off, lsmck_apply_get* gets, lsmck_get_query* miss_q, uint32_t* miss_get,
+                  hipStream_t st);
+// segs[g] = {0, nent, 0}: an open segment, before the emit writes what it knows of it
+int lsmk_apl_open_seg(lsmck_write_seg* segs, uint64_t g, uint64_t nent, hipStream_t st);
 int lsmk_launch_crc32_fixed(const lsmck::CrcParams* P, int ncu, int variant, hipStream_t st);
 int lsmk_launch_sha256(const lsmck::ShaParams* P, hipStream_t st);
 int lsmk_launch_sha256_slices(const lsmck::ShaSliceParams* P, hipStream_t st);

@@ -384,6 +384,25 @@ extern "C" int lsmk_wpl_mark(const WplWs* Pp, uint64_t n, uint32_t block, const 
   return 0;
 }
 
+// lsmk_wpl_mark's first half alone, for lsmck_db_apply_plan, whose entry flags
+// are its own: the marks and the segment numbers
+extern "C" int lsmk_wpl_number(const WplWs* Pp, uint64_t n, uint32_t block, const uint32_t* elist,
+                               const unsigned long long* cinfo, const uint32_t* bfirst, void* tmp, size_t* tmp_bytes,
+                               hipStream_t st) {
+  const WplWs& P = *Pp;
+  const bool query = tmp == nullptr;
+  if (!query) {
+    const unsigned nblk = (unsigned)((n + block - 1u) / block);
+    hipLaunchKernelGGL(wpl_mark, dim3(nblk), dim3(256), 4 * (size_t)block, st, P, n, block, elist, cinfo, bfirst);
+    if (int rc = wpl_launch_err()) return rc;
+  }
+  size_t b = query ? 0 : *tmp_bytes;
+  const hipError_t e = rocprim::inclusive_scan(tmp, b, P.mark, P.seg1, n, rocprim::plus<uint32_t>(), st);
+  if (e != hipSuccess) return wpl_err(e);
+  if (query) *tmp_bytes = std::max<size_t>(b, 1);
+  return 0;
+}
+
 // ents, src (optional) and segs (nseg items, one more behind a last command
 // that flushed: closed).  tmp == nullptr: *tmp_bytes alone
 extern "C" int lsmk_wpl_emit(const WplWs* Pp, const lsmck_wal_cmd* cmds, uint64_t n, uint64_t nent, uint64_t nseg,

@@ -138,6 +138,18 @@ class WritePlanError(_lib.LsmckError):
         super().__init__(rc, f"{what} (bad_index={bad_index}, needed={needed})")
 
 
+class ApplyPlanError(_lib.LsmckError):
+    """lsmck_db_apply_plan refused the stream: ``bad_index`` is the first
+    invalid command (LSMCK_EINVAL; None when the tombstone byte is missing or
+    an argument is wrong), or ``needed`` = (entries, flushes, gets, misses)
+    when an array given holds fewer (LSMCK_ENOSPC); the other one is None."""
+
+    def __init__(self, rc, what, bad_index=None, needed=None):
+        self.bad_index = bad_index
+        self.needed = needed
+        super().__init__(rc, f"{what} (bad_index={bad_index}, needed={needed})")
+
+
 class SstDecodeError(_lib.LsmckError):
     """lsmck_sstable_decode_batch refused the batch: ``bad_index`` is the first
     table whose span is refused (LSMCK_EINVAL; None for an argument error), or
@@ -886,6 +898,56 @@ class Context:
         fewer than segs must hold); nothing was written then."""
         return self._write_plan(keys_ptr, keys_bytes, vals_ptr, vals_bytes, cmds_ptr, n, limit, tomb_off, ents_ptr,
                                 ent_cap, src_ptr, segs_ptr, seg_cap, _lib.DEVICE)
+
+    def _apply_plan(self, keys, kb, vals, vb, cmds, n, limit, tomb_off, ents, ent_cap, src, segs, seg_cap, gets,
+                    get_cap, miss_q, miss_get, flags):
+        none = 2 ** 64 - 1
+        nent, nflush, nget, nmiss, bad = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_uint64(none)
+        rc = self.lib.lsmck_db_apply_plan(self.handle, keys, kb, vals, vb, cmds, n, limit, tomb_off, ents, ent_cap, src,
+                                          segs, seg_cap, gets, get_cap, miss_q, miss_get, C.byref(nent),
+                                          C.byref(nflush), C.byref(nget), C.byref(nmiss), C.byref(bad), flags)
+        if rc == _lib.EINVAL:
+            raise ApplyPlanError(rc, "db_apply_plan", bad_index=None if bad.value == none else bad.value)
+        if rc == _lib.ENOSPC:
+            raise ApplyPlanError(rc, "db_apply_plan", needed=(nent.value, nflush.value, nget.value, nmiss.value))
+        _lib.check(rc, "db_apply_plan")
+        return nent.value, nflush.value, nget.value, nmiss.value
+
+    def db_apply_plan(self, keys, vals, cmds, limit, tomb_off, pinned=False):
+        """lsmck_db_apply_plan, host form: ``db_write_plan`` over a stream
+        that also holds Gets (type ``_lib.CMD_GET``), each answered by the
+        last write in front of it.  Returns (ents, src, segs as
+        ``db_write_plan`` does; gets: APPLY_GET_DTYPE, the Gets in stream
+        order; miss_q: GET_QUERY_DTYPE over ``keys`` and miss_get: np.uint32,
+        the Gets no write of the stream answers).  Raises ApplyPlanError."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint8)
+        vals = keys if vals is keys else np.ascontiguousarray(vals, dtype=np.uint8)
+        cmds = np.ascontiguousarray(cmds, dtype=_lib.WAL_CMD_DTYPE)
+        n = len(cmds)
+        ents = np.empty(n, dtype=_lib.WAL_CMD_DTYPE)
+        src = np.empty(n, dtype=np.uint32)
+        segs = np.empty(n + 1, dtype=_lib.WRITE_SEG_DTYPE)
+        gets = np.empty(n, dtype=_lib.APPLY_GET_DTYPE)
+        miss_q = np.empty(n, dtype=_lib.GET_QUERY_DTYPE)
+        miss_get = np.empty(n, dtype=np.uint32)
+        flags = _lib.HOST_PINNED if pinned else _lib.HOST
+        nent, nflush, nget, nmiss = self._apply_plan(
+            _p(keys), keys.nbytes, _p(vals), vals.nbytes, _p(cmds), n, limit, tomb_off, ents.ctypes.data, n,
+            src.ctypes.data, segs.ctypes.data, n + 1, gets.ctypes.data, n, miss_q.ctypes.data, miss_get.ctypes.data,
+            flags)
+        return ents[:nent], src[:nent], segs[:nflush + 1], gets[:nget], miss_q[:nmiss], miss_get[:nmiss]
+
+    def db_apply_plan_device(self, keys_ptr, keys_bytes, vals_ptr, vals_bytes, cmds_ptr, n, limit, tomb_off, ents_ptr,
+                             ent_cap, src_ptr, segs_ptr, seg_cap, gets_ptr, get_cap, miss_q_ptr=None,
+                             miss_get_ptr=None):
+        """lsmck_db_apply_plan on device pointers (as ``db_write_plan_device``;
+        gets: get_cap lsmck_apply_get; miss_q / miss_get: get_cap
+        lsmck_get_query / u32, both or neither).  Returns (nent, nflush, nget,
+        nmiss); raises ApplyPlanError with ``bad_index`` or ``needed`` = the
+        four counts; nothing was written then."""
+        return self._apply_plan(keys_ptr, keys_bytes, vals_ptr, vals_bytes, cmds_ptr, n, limit, tomb_off, ents_ptr,
+                                ent_cap, src_ptr, segs_ptr, seg_cap, gets_ptr, get_cap, miss_q_ptr, miss_get_ptr,
+                                _lib.DEVICE)
 
     def wal_recs_to_cmds_device(self, recs_ptr, n, img_bytes, cmds_ptr, stream=None):
         """lsmck_wal_recs_to_cmds: n compact replay records (lsmck_wal_rec16,
